@@ -17,6 +17,9 @@ Extra objects on the JSON line: "roofline" (the select+expand+backup kernel, HIP
 bytes from live engine counters, SURVEY.md §8d formula), "cpu_baseline" (the C oracle + PyTorch-CPU net on the host
 cores, bounded sample, rank 0 at N=1 only) and "secondary" (the north star's second target, Santorini no-gods, same
 engine, shorter window, with its own roofline).
+
+`--dump-outputs DIR` writes the example records the timed steps produced as DIR/<name>.npy (see dump_arrays), so that two builds can
+be compared output for output on the same arguments.
 """
 import argparse
 import json
@@ -60,6 +63,7 @@ NET_MFLOP_PER_LEAF = {'splendor2': 1.042, 'azul': 0.408, 'santorini1': 18.52, 's
 # numMCTSSims // ratio_fullMCTS simulations, MCTS.py:58-59), so that games END inside a short timed window and the episode-end
 # example gather carries data; about 3/4 of a typical game
 PREROLL_PLIES = {'splendor2': 40, 'splendor4': 70, 'santorini1': 14, 'santorini11': 16, 'azul': 50}
+DUMP_BYTES = 64 * 10 ** 6       # --dump-outputs: at most this much in all
 
 
 def algorithmic_bytes_per_sim(S, A, P, d, vbar, e):
@@ -172,7 +176,7 @@ def respawn_ranks(n):
     return rc
 
 
-def build_engine(a, game_key, T, rank, dev):
+def build_engine(a, game_key, T, rank, dev, deterministic=False):
     """game + engine-kernel net + SelfPlayEngine for one of the hot-path configs"""
     import torch
     from azg_amd import games
@@ -216,11 +220,14 @@ def build_engine(a, game_key, T, rank, dev):
     eng = None
     for attempt in range(3):           # the forest wants a large share of the 288 GB HBM: shrink the arena if the device has less to give
         try:
+            # deterministic (the leg --dump-outputs writes): per-tree budgets in the pipeline, so that which games have ended -- and so
+            # the examples -- is a function of the arguments alone; with the default work-sharing budget it depends on GPU timing
             eng = SelfPlayEngine(game, net, margs, T, node_capacity=cap, max_examples=T * 160, rng_seed=2026,
                                  stream0=rank * T, use_graph=not a.no_graph, level_budget=a.level_budget, groups=a.groups,
                                  work_budget=None if a.work_budget < 0 else a.work_budget, advance_every=a.advance_every or None,
                                  pin_xcd=None if not a.no_pin_xcd else False,
-                                 async_pipe=None if getattr(a, 'async_pipe', -1) < 0 else bool(a.async_pipe))
+                                 async_pipe=None if getattr(a, 'async_pipe', -1) < 0 else bool(a.async_pipe),
+                                 deterministic=True if deterministic else None)
             break
         except Exception as ex:        # azg_amd.AzgError: hipMalloc failed
             if a.node_capacity or attempt == 2:
@@ -404,12 +411,30 @@ def measure_net(a, eng, T, game_key, net_kind):
                 flops_per_launch=flops, leaves_per_launch=Tg, net_ms=ms, launches=n, standalone_launch_ms=standalone_ms)
 
 
-def run_workload(a, game_key, T, steps, warmup, rank, world, dev, use_dist, roofline=True, preroll_override=None):
-    """warm-up ply waves, then exactly `steps` timed ply waves bracketed by barrier + synchronize; -> result dict (rank-reduced)"""
+def dump_arrays(ex, seed=0):
+    """the example records the timed region drained (Coach.py:76-82: board, pi, z, valids, q) and their keys (global game stream, game
+    index on it, ply, player) as float arrays in key order -- the drain order follows the order in which the trees finished.  Beyond
+    DUMP_BYTES: a sample of the records drawn with a fixed seed.  -> ({name: array}, number of records drained)"""
+    import numpy as np
+    cols = [t.cpu().numpy() for t in ex]
+    meta = cols[5]
+    order = np.lexsort((meta[:, 3], meta[:, 2], meta[:, 1], meta[:, 0]))
+    n = len(order)
+    row_bytes = 4 * sum(int(np.prod(c.shape[1:])) for c in cols[:5]) + 8 * meta.shape[1]
+    cap = (DUMP_BYTES - 64 * 1024) // row_bytes            # (room for the .npy headers)
+    if n > cap:
+        order = order[np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))]
+    names = ('boards', 'pi', 'z', 'valids', 'q', 'meta')
+    return {k: c[order].astype(np.float64 if k == 'meta' else np.float32) for k, c in zip(names, cols)}, n
+
+
+def run_workload(a, game_key, T, steps, warmup, rank, world, dev, use_dist, roofline=True, preroll_override=None, dump=False):
+    """warm-up ply waves, then exactly `steps` timed ply waves bracketed by barrier + synchronize; -> result dict (rank-reduced).
+    dump: the engine in its deterministic mode, and res['outputs'] (rank 0) = dump_arrays of what the timed region drained"""
     import torch
     import torch.distributed as dist
     from azg_amd.selfplay import gather_examples
-    eng, margs, label, weights, net_kind = build_engine(a, game_key, T, rank, dev)
+    eng, margs, label, weights, net_kind = build_engine(a, game_key, T, rank, dev, deterministic=dump)
     eng.game_key = game_key
     sims = a.sims
     eng.start()
@@ -464,6 +489,7 @@ def run_workload(a, game_key, T, steps, warmup, rank, world, dev, use_dist, roof
         loc[2] = sum(int(x) << b for b, x in enumerate(bits.tolist()))
     tot_sims, tot_plies, errs, tot_games, tot_examples, dropped = [int(x) for x in loc.tolist()]
     assert tot_plies > 0, 'no ply completed inside the timed region: raise --steps'
+    outputs = dump_arrays(ex) if dump and rank == 0 else None         # (rank 0 holds every rank's records after the gather)
     res = dict(label=label, weights=weights, net_kind=net_kind, value=tot_plies / dt, value_from_sims=tot_sims / sims / dt,
                dt=dt, sims_per_sec=tot_sims / dt, plies_completed=tot_plies, games_finished=tot_games,
                examples_gathered=tot_examples if world == 1 else int(ex[0].shape[0]), examples_dropped=dropped,
@@ -471,7 +497,7 @@ def run_workload(a, game_key, T, steps, warmup, rank, world, dev, use_dist, roof
                max_live_after_gc=int(s1.get('max_live_after_gc', 0)), max_nodes_per_tree=s1['max_nodes'],
                gc_runs=s1['gc_runs'], hip_graph=eng.graph is not None, rounds_timed=steps * sims,
                ms_per_round=dt / (steps * sims) * 1e3, preroll_plies=preroll, work_budget=eng.work_budget, advance_every=eng.K, node_capacity=eng.forest.cfg.node_capacity,
-               max_live_frac=int(s1.get('max_live_after_gc', 0)) / max(1, eng.forest.cfg.node_capacity))
+               max_live_frac=int(s1.get('max_live_after_gc', 0)) / max(1, eng.forest.cfg.node_capacity), outputs=outputs)
     if use_dist:
         # proof that the collective saw every rank, and what it cost (inside the timed region): world size as the process group reports
         # it, the record count every rank contributed (from the count all_gather), the bytes rank 0 received, the wall time of the exchange
@@ -540,6 +566,10 @@ def main():
     ap.add_argument('--no-sustained', action='store_true', help='skip the whole-games leg (value_whole_games)')
     ap.add_argument('--sustained-steps', type=int, default=70, help='timed ply waves of the whole-games leg')
     ap.add_argument('--secondary-steps', type=int, default=0, help='timed ply waves of the secondary leg (0 = max(3, steps // 5))')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the example records they produced (boards, pi, z, valids, q and their keys, meta) as '
+                         'DIR/<name>.npy, float32 (meta float64), in key order, a seeded sample beyond 64 MB; the headline leg then runs '
+                         'the engine in its deterministic mode (per-tree budgets), so that the same arguments give the same records')
     a = ap.parse_args()
     if a.traffic_json is None:
         import glob
@@ -575,7 +605,16 @@ def main():
     T = a.games
     if os.environ.get('AZG_BENCH_FAIL_RANK') and int(os.environ['AZG_BENCH_FAIL_RANK']) == rank:
         raise SystemExit('AZG_BENCH_FAIL_RANK: rank %d dies on purpose (tests/test_gpu_bench_ranks.py)' % rank)
-    r = run_workload(a, a.game, T, a.steps, a.warmup, rank, world, dev, use_dist)
+    r = run_workload(a, a.game, T, a.steps, a.warmup, rank, world, dev, use_dist, dump=bool(a.dump_outputs))
+    dumped = None
+    if r['outputs'] is not None:
+        import numpy as np
+        arrays, n_records = r['outputs']
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for k, v in arrays.items():
+            np.save(os.path.join(a.dump_outputs, k + '.npy'), v)
+        dumped = dict(dir=a.dump_outputs, records=n_records, records_written=len(arrays['meta']), deterministic=True,
+                      bytes=sum(v.nbytes for v in arrays.values()))
     search_mix = ('every ply a full search' if a.prob_full >= 1.0 else
                   'prob_fullMCTS=%g: full searches mixed with numMCTSSims//5 fast ones (reference default mix, secondary figure)' % a.prob_full)
     net_txt = ('engine kernel, fp32-accurate: f16 hi+lo split-precision MFMA on token-major tiles' if r['net_kind'] == 'hip' and a.game == 'splendor2'
@@ -612,6 +651,8 @@ def main():
         out['roofline'] = r['roofline']
     if r.get('roofline_net'):
         out['roofline_net'] = r['roofline_net']
+    if dumped:
+        out['dump_outputs'] = dumped
     if use_dist:
         dist.barrier()
     # ---- sustained: the same workload over WHOLE games (no pre-roll: opening, middle game, endgame, restart), no roofline legs -- the
