@@ -17,6 +17,7 @@
 #include "nn_v80_h2.hip.h"
 #include "nn_mb1d.hip.h"
 #include "nn_conv5x5.hip.h"
+#include "nn_abalone.hip.h"
 
 using namespace azg;
 
@@ -459,6 +460,24 @@ extern "C" int azg_nn_s78_forward_split(const int8_t* boards, const uint8_t* val
 extern "C" int azg_nn_s78_forward_h2(const int8_t* boards, const uint8_t* valid, const float* const* w, float ds_e, float ds_p, int n_blocks,
                                      int A, int P, int B, float* pi, float* v, void* stream) {
     return s78_launch(boards, valid, w, n_blocks, A, P, B, pi, v, stream, 2, ds_e, ds_p);
+}
+
+// ---- Abalone net V21 (4 InvertedResidual blocks on the 9 x 9 grid, A = 3402, P = 2): one launch, 4 samples per workgroup (nn_abalone.hip.h) ----
+extern "C" int azg_nn_aba21_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_blocks, int A, int P, int B,
+                                    float* pi, float* v, void* stream) {
+    if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_aba21_forward: null/empty argument");
+    if (n_blocks != 4 || A != ABA_A || P != 2) return fail("azg_nn_aba21_forward: built for 4 blocks, A = 3402, P = 2");
+    for (int i = 0; i < 16; i++)
+        if (!w[i]) return fail("azg_nn_aba21_forward: null weight pointer");
+    Aba21NetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], w[15]};
+    static bool attr = false;
+    if (!attr) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_aba21_net<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ABA_LDS));
+        attr = true;
+    }
+    k_aba21_net<4, 2><<<dim3((B + ABA_NS - 1) / ABA_NS), dim3(ABA_THREADS), ABA_LDS, (hipStream_t)stream>>>(N, boards, valid, B, pi, v);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int azg_nn_board_to_x_ld(const int8_t* boards, float* x, int B, int C, int L, int ldx, void* stream) {

@@ -1015,6 +1015,147 @@ class SantoriniV78Hip(SantoriniV89Hip):
 
 
 
+class AbaloneV21:
+    """abalone/AbaloneNNet.py nn_version 21 (:120-160, forward :173-201) -- the net of pretrained_BelgianDaisy.pt: the 3 spatial
+    planes (marbles of each player, hex mask) of the (9, 9, 4) board -> conv3x3(3->24)+BN+ReLU -> 4 torchvision InvertedResidual
+    blocks (1x1 expand 24->48 + BN + ReLU, depthwise 3x3 + BN + ReLU, 1x1 project + BN, residual; no SE) -> policy 1x1 conv
+    24->42 + BN laid out [9][9][42]; value 1x1 conv 24->4 + BN + ReLU flattened channel-major, concatenated with a 16-wide
+    embedding of the 6 metadata values (Linear(6,16)+ReLU), -> 64 -> P.  BatchNorm (eps 1e-5) folded; plain torch ops."""
+
+    def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
+        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        self.P, self.A = num_players, 81 * sd['head_PI.0.weight'].shape[0]
+
+        def conv_bn(conv, bn):
+            s, b = _fold_bn(sd, bn)
+            return (sd[conv + '.weight'] * s[:, None, None, None]).contiguous(), b
+        self.c0 = conv_bn('first_layer.0', 'first_layer.1')
+        self.blocks = []
+        i = 0
+        while 'trunk.%d.block.0.0.weight' % i in sd:
+            self.blocks.append(tuple(conv_bn('trunk.%d.block.%d.0' % (i, j), 'trunk.%d.block.%d.1' % (i, j)) for j in range(3)))
+            i += 1
+        self.hp = conv_bn('head_PI.0', 'head_PI.1')
+        self.hv = conv_bn('head_V_conv.0', 'head_V_conv.1')
+        self.meta = (sd['meta_fc.0.weight'].t().contiguous(), sd['meta_fc.0.bias'])
+        self.fc_v1 = (sd['head_V_fc.0.weight'].t().contiguous(), sd['head_V_fc.0.bias'])
+        self.fc_v2 = (sd['head_V_fc.2.weight'].t().contiguous(), sd['head_V_fc.2.bias'])
+        self.to(device, dtype)
+
+    def to(self, device, dtype=torch.float32):
+        self.device, self.dtype = torch.device(device), dtype
+        mv = lambda pr: tuple(t.to(self.device, dtype) for t in pr)  # noqa: E731
+        self.c0, self.hp, self.hv, self.meta = mv(self.c0), mv(self.hp), mv(self.hv), mv(self.meta)
+        self.blocks = [tuple(mv(c) for c in blk) for blk in self.blocks]
+        self.fc_v1, self.fc_v2 = mv(self.fc_v1), mv(self.fc_v2)
+        return self
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        z = np.load(path)
+        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        B = boards.shape[0]
+        x = boards.reshape(B, 9, 9, 4).to(self.dtype)
+        meta = F.relu(torch.addmm(self.meta[1], x[:, 0, 0:6, 3], self.meta[0]))
+        x = F.relu(F.conv2d(x[..., :3].permute(0, 3, 1, 2).contiguous(), self.c0[0], self.c0[1], padding=1))
+        for (we, be), (wd, bd), (wp, bp) in self.blocks:
+            h = F.relu(F.conv2d(x, we, be))
+            h = F.relu(F.conv2d(h, wd, bd, padding=1, groups=wd.shape[0]))
+            x = F.conv2d(h, wp, bp) + x
+        logits = F.conv2d(x, self.hp[0], self.hp[1]).permute(0, 2, 3, 1).reshape(B, self.A).float()
+        hv = torch.cat([F.relu(F.conv2d(x, self.hv[0], self.hv[1])).flatten(1), meta], dim=1)
+        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).float())
+        logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
+        return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
+        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+class AbaloneV21Hip:
+    """AbaloneV21 (4 InvertedResidual blocks on the 9 x 9 grid, A = 3402) evaluated by the engine's one-launch kernel
+    (azg_nn_aba21_forward, csrc/nn_abalone.hip.h: f32 MFMA GEMMs for the convolutions, the depthwise 3x3 on the vector ALUs, heads
+    and masked softmax in the same launch) instead of ~20 MIOpen / hipBLASLt launches.  Wraps an AbaloneV21; static pi / v buffers
+    (HIP-graph capture of the engine's rounds)."""
+
+    def __init__(self, base, max_batch=4096):
+        import ctypes as C
+        from . import _lib
+        self._lib, self.base, self.device = _lib, base, base.device
+        self.P, self.A = base.P, base.A
+        assert base.dtype == torch.float32 and self.device.type == 'cuda' and len(base.blocks) == 4 and self.A == 3402 and self.P == 2
+        keep = self.pack(base)
+        self._keep = keep
+        self.ptrs = (C.c_void_p * 16)(*[t.data_ptr() for t in keep])
+        self._alloc(max_batch)
+
+    @staticmethod
+    def pack(base):
+        """the 16 weight tensors of azg_nn_aba21_forward (include/azg.h), on base's device"""
+        d = base.device
+
+        def frag(m, G, nct):               # [K][N] -> [nct][G][64 lanes], element = m[G * (lane >> 4) + j][16 * ct + (lane & 15)] (zero padded)
+            z = torch.zeros((4 * G, 16 * nct), dtype=torch.float32, device=d)
+            z[:m.shape[0], :m.shape[1]] = m
+            return z.view(4, G, nct, 16).permute(2, 1, 0, 3).contiguous().view(-1)
+        cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]).contiguous()  # noqa: E731
+        wh = torch.cat([base.hp[0].reshape(42, 24).t(), base.hv[0].reshape(4, 24).t()], dim=1)
+        bh = torch.zeros(48, dtype=torch.float32, device=d)
+        bh[:42], bh[42:46] = base.hp[1], base.hv[1]
+        keep = [frag(base.c0[0].permute(2, 3, 1, 0).reshape(27, 24), 8, 2), base.c0[1].contiguous(),
+                cat([frag(we.reshape(48, 24).t(), 6, 3) for (we, _), _, _ in base.blocks]), cat([be for (_, be), _, _ in base.blocks]),
+                cat([wd.reshape(48, 9) for _, (wd, _), _ in base.blocks]), cat([bd for _, (_, bd), _ in base.blocks]),
+                cat([frag(wp.reshape(24, 48).t(), 12, 2) for _, _, (wp, _) in base.blocks]), cat([bp for _, _, (_, bp) in base.blocks]),
+                frag(wh, 6, 3), bh, base.meta[0].contiguous(), base.meta[1].contiguous(),
+                base.fc_v1[0].contiguous(), base.fc_v1[1].contiguous(), base.fc_v2[0].contiguous(), base.fc_v2[1].contiguous()]
+        assert tuple(base.fc_v1[0].shape) == (340, 64) and tuple(base.meta[0].shape) == (6, 16)
+        return keep
+
+    def _alloc(self, B):
+        self.maxB = B
+        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+
+    def clone_buffers(self):
+        import copy
+        other = copy.copy(self)
+        other._alloc(self.maxB)
+        return other
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        import ctypes as C
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        boards = boards.reshape(B, -1)
+        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 324
+        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+        assert valids.shape == (B, self.A) and valids.is_cuda
+        self._lib.check(self._lib.lib().azg_nn_aba21_forward(p(boards), p(valids), self.ptrs, 4, self.A, self.P, B, p(self.pi), p(self.v),
+                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self.pi[:B], self.v[:B]
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
 class TorchModuleEvaluator:
     """Leaf evaluator around ANY torch module with the reference's forward signature
     `module(board f32[B, *board_shape], valid_actions bool[B, A]) -> (log_pi f32[B, A], v f32[B, P])` -- the torch branch of

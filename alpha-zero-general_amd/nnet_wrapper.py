@@ -23,7 +23,8 @@ import torch
 
 from . import _lib, nnet as _nn, train as _train
 
-# nn_version -> trainable module per game (splendor/SplendorNNet.py V80, azul/AzulNNet.py V84, santorini/SantoriniNNet.py V89/V78)
+# nn_version -> trainable module per game (splendor/SplendorNNet.py V80, azul/AzulNNet.py V84, santorini/SantoriniNNet.py V89/V78,
+# abalone/AbaloneNNet.py V21)
 _DEFAULT_VERSION = {(_lib.SPLENDOR, 2): 80, (_lib.SPLENDOR, 3): 80, (_lib.SPLENDOR, 4): 80, (_lib.AZUL, 2): 84,
                     (_lib.SANTORINI, 1): 89, (_lib.SANTORINI, 11): 78}
 
@@ -38,7 +39,10 @@ def _module_for(game, version, dropout):
         return _train.SantoriniV89Module(P, A, dropout)
     if gid == _lib.SANTORINI and version == 78 and game.variant == 11:
         return _train.SantoriniV78Module(P, A, dropout)
-    raise ValueError('nn_version %r is not built for this game (engine nets: Splendor 80, Azul 84, Santorini 89 no-gods / 78 with gods)'
+    if gid == _lib.ABALONE and version == 21:
+        return _train.AbaloneV21Module(P, A, dropout)
+    raise ValueError('nn_version %r is not built for this game (engine nets: Splendor 80, Azul 84, Santorini 89 no-gods / 78 with gods, '
+                     'Abalone 21)'
                      % (version,))
 
 
@@ -46,8 +50,11 @@ def evaluator_for(module, game, max_batch):
     """engine-kernel evaluator (one launch per leaf batch) of a trainable module's current weights"""
     sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
     dev, ver = str(game.device), getattr(module, 'version', 80)
-    if not isinstance(module, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module)):
+    if not isinstance(module, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
+                               _train.AbaloneV21Module)):
         return _nn.TorchModuleEvaluator(module, game, max_batch)
+    if ver == 21:
+        return _nn.AbaloneV21Hip(_nn.AbaloneV21(sd, device=dev), max_batch=max_batch)
     if ver == 84:
         return _nn.MobileNet1dHip(_nn.AzulV84(sd, num_players=game.P, device=dev), max_batch=max_batch)
     if ver == 89:

@@ -205,6 +205,32 @@ class SantoriniV78Module(nn.Module):
         pi = torch.where(valid_actions.bool(), self.head_PI(f, meta), self.lowvalue)
         return F.log_softmax(pi, dim=1), torch.tanh(v)
 
+class AbaloneV21Module(nn.Module):
+    """abalone/AbaloneNNet.py nn_version 21 (:120-160, forward :173-201; Belgian Daisy, A = 3402) with the reference's parameter
+    names: conv3x3(3->24)+BN+ReLU, four InvertedResidual blocks 24 -> 48 -> 24, meta_fc (6 metadata values -> 16), policy 1x1
+    conv 24->42 + BN, value 1x1 conv 24->4 + BN + ReLU -> Linear(340, 64) + ReLU -> Linear(64, P)."""
+    version = 21
+
+    def __init__(self, num_players=2, action_size=3402, dropout=0.0):
+        super().__init__()
+        self.P, self.A, self.dropout = num_players, action_size, dropout
+        self.first_layer = nn.Sequential(nn.Conv2d(3, 24, 3, padding=1, bias=False), nn.BatchNorm2d(24), nn.ReLU())
+        self.trunk = nn.Sequential(*[_MBBlock2d(24, 48) for _ in range(4)])
+        self.meta_fc = nn.Sequential(nn.Linear(6, 16), nn.ReLU())
+        self.head_PI = nn.Sequential(nn.Conv2d(24, action_size // 81, 1, bias=False), nn.BatchNorm2d(action_size // 81))
+        self.head_V_conv = nn.Sequential(nn.Conv2d(24, 4, 1, bias=False), nn.BatchNorm2d(4), nn.ReLU())
+        self.head_V_fc = nn.Sequential(nn.Linear(4 * 81 + 16, 64), nn.ReLU(), nn.Linear(64, num_players))
+        self.register_buffer('lowvalue', torch.FloatTensor([-1e8]))
+
+    def forward(self, boards, valid_actions):
+        x = boards.reshape(-1, 9, 9, 4).float()
+        meta = self.meta_fc(x[:, 0, 0:6, 3])
+        f = self.trunk(self.first_layer(x[..., :3].permute(0, 3, 1, 2)))
+        pi = self.head_PI(f).permute(0, 2, 3, 1).flatten(1)
+        v = self.head_V_fc(torch.cat([torch.flatten(self.head_V_conv(f), 1), meta], dim=1))
+        pi = torch.where(valid_actions.bool(), pi, self.lowvalue)
+        return F.log_softmax(pi, dim=1), torch.tanh(v)
+
 
 def loss_pi(target_pi, out_log_pi):                                            # GenericNNetWrapper.py:179-181
     return F.kl_div(out_log_pi, target_pi, reduction='batchmean')

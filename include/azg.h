@@ -439,6 +439,18 @@ int azg_nn_s78_forward_split(const int8_t* boards_dev, const uint8_t* valid_dev,
    16 samples per workgroup, no workspace).  Same 1e-5 contract. */
 int azg_nn_s78_forward_h2(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, float ds_e, float ds_p, int n_blocks,
                           int A, int P, int B, float* pi_dev, float* v_dev, void* stream);
+/* The Abalone net (nn_version 21, abalone/AbaloneNNet.py:120-160,173-201; Belgian Daisy): ONE launch on `stream`, 4 samples per
+   workgroup (nn_abalone.hip.h).  boards int8 [B][9][9][4] (planes 0, 1 = marbles, 2 = hex mask, 3 = metadata: board[0][0..5][3]),
+   valid u8 [B][A] -> pi f32 [B][A] (masked softmax, action = (r*9 + q)*42 + plane), v f32 [B][P] (tanh).
+   w = 16 device pointers {W0, b0, We, be, Wd, bd, Wp, bp, Wh, bh, Wm, bm, Wf1, bf1, Wf2, bf2}, BatchNorm folded, f32:
+   W0 [2][8][64] = first conv fragment element W0[k = 8*(lane>>4) + m][16*ct + (lane&15)], k = tap*3 + c (zero for k >= 27), b0[24];
+   We per block [3][6][64] element We[6*(lane>>4) + m][16*ct + (lane&15)], be [4][48]; Wd [4][48][9], bd [4][48];
+   Wp per block [2][12][64] element Wp[12*(lane>>4) + m][16*ct + (lane&15)] (columns >= 24 zero), bp [4][24];
+   Wh [3][6][64] = the two head convolutions as one 24 x 48 matrix (columns 0..41 policy, 42..45 value, 46..47 zero), bh [48];
+   Wm [6][16], bm[16]; Wf1 [340][64] (row = c*81 + cell, then the 16 meta features), bf1[64]; Wf2 [64][P], bf2[P].
+   f32 MFMA operands: the full f32 range, same 1e-5 contract as the torch net.  n_blocks must be 4, A 3402, P 2. */
+int azg_nn_aba21_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_blocks, int A, int P, int B,
+                         float* pi_dev, float* v_dev, void* stream);
 /* boards int8 [B][C][7] (reference board layout) -> x f32 [B][7][C] */
 int azg_nn_board_to_x(const int8_t* boards_dev, float* x_dev, int B, int C, void* stream);
 /* boards int8 [B][C][L] -> x f32 [B][L][ldx], columns C..ldx-1 zeroed (row stride padded to a multiple of 4 floats) */

@@ -54,8 +54,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--net', default='hash', choices=['hash', 'hashhip', 'mlp', 'engine', 'torchnet'],
                     help='leaf evaluator: integer hash-net as torch ops, the same as one engine kernel (azg_eval_hashnet), MlpNet through TorchModuleEvaluator, '
-                         'engine = the game\'s SHIPPED net (minivilles/pretrained_2players.pt V82, thelittleprince/pretrained_3players.pt V83) as one launch of '
-                         'the engine\'s MobileNet-1d kernel (nn_mb1d.hip.h); torchnet = the same weights as PyTorch-ROCm ops (nnet.MobileNet1d)')
+                         'engine = the game\'s SHIPPED net (minivilles/pretrained_2players.pt V82, thelittleprince/pretrained_3players.pt V83: the engine\'s '
+                         'MobileNet-1d kernel, nn_mb1d.hip.h; abalone/pretrained_BelgianDaisy.pt V21: nn_abalone.hip.h) as one launch; torchnet = the '
+                         'same weights as PyTorch-ROCm ops (nnet.MobileNet1d, nnet.AbaloneV21)')
     ap.add_argument('--md', action='store_true', help='markdown table row instead of JSON')
     ap.add_argument('--games', type=int, default=1024)
     ap.add_argument('--sims', type=int, default=200)
@@ -72,12 +73,17 @@ def main():
         args = Args(numMCTSSims=a.sims, cpuct=1.0, fpu=0.0, universes=1, forced_playouts=name != 'akropolis', prob_fullMCTS=1.0, ratio_fullMCTS=5,
                     dirichletAlpha=0.3, temperature=[1.25, 0.8, 1.0], tempThreshold=6)
         if a.net in ('engine', 'torchnet'):
-            tag = {'minivilles': 'minivilles2_v82', 'thelittleprince': 'tlp3_v83'}.get(name)
+            tag = {'minivilles': 'minivilles2_v82', 'thelittleprince': 'tlp3_v83', 'abalone': 'abalone_v21'}.get(name)
             if tag is None:
                 continue
             from azg_amd import nnet
-            base = nnet.MobileNet1d.from_npz(os.path.join(ROOT, 'tests', 'golden', 'weights_%s.npz' % tag), device='cuda:0')
-            net = nnet.MobileNet1dHip(base, max_batch=T) if a.net == 'engine' else base
+            w = os.path.join(ROOT, 'tests', 'golden', 'weights_%s.npz' % tag)
+            if name == 'abalone':           # abalone/pretrained_BelgianDaisy.pt V21: the engine's one-launch kernel (nn_abalone.hip.h)
+                base = nnet.AbaloneV21.from_npz(w, device='cuda:0')
+                net = nnet.AbaloneV21Hip(base, max_batch=T) if a.net == 'engine' else base
+            else:
+                base = nnet.MobileNet1d.from_npz(w, device='cuda:0')
+                net = nnet.MobileNet1dHip(base, max_batch=T) if a.net == 'engine' else base
         elif a.net == 'mlp':
             from azg_amd.nnet import TorchModuleEvaluator
             torch.manual_seed(0)

@@ -1,4 +1,5 @@
-"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets (HIP events, 50 forwards after warm-up)."""
+"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets and the Abalone net (HIP events,
+50 forwards after warm-up)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -48,3 +49,19 @@ valids = (torch.rand((Tg, 1782), device='cuda:0') < 0.1).to(torch.uint8)
 valids[:, 0] = 1
 print('santorini11 V78 T=%d' % Tg, 'torch ops (MIOpen) %.1f us' % timed(base, boards, valids.bool(), 5),
       ' k_s78_net %.1f us' % timed(nnet.SantoriniV78Hip(base, max_batch=Tg), boards, valids), flush=True)
+
+# Abalone V21 at T: the plain-torch net (BN folded), the one-launch kernel, and the trainable module through TorchModuleEvaluator (the path
+# of a game without an engine net: BN unfolded, log_softmax + exp)
+from azg_amd import games, train  # noqa: E402
+import numpy as np  # noqa: E402
+base = nnet.AbaloneV21.from_npz(G + '/weights_abalone_v21.npz', device='cuda:0')
+d = np.load(G + '/netfwd_abalone_v21.npz')
+idx = np.arange(T) % len(d['boards'])
+boards = torch.from_numpy(d['boards'][idx].reshape(T, -1)).to('cuda:0')
+valids = torch.from_numpy(d['masks'][idx]).to('cuda:0')
+z = np.load(G + '/weights_abalone_v21.npz')
+mod = train.AbaloneV21Module()
+mod.load_state_dict({k[3:]: torch.as_tensor(z[k]) for k in z.files if k.startswith('sd/')}, strict=True)
+print('abalone V21 T=%d' % T, 'torch ops (MIOpen) %.1f us' % timed(base, boards, valids.bool(), 10),
+      ' k_aba21_net %.1f us' % timed(nnet.AbaloneV21Hip(base, max_batch=T), boards, valids),
+      ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.AbaloneGame()), boards, valids, 10), flush=True)
