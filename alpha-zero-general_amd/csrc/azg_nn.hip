@@ -18,6 +18,7 @@
 #include "nn_mb1d.hip.h"
 #include "nn_conv5x5.hip.h"
 #include "nn_abalone.hip.h"
+#include "nn_smallworld.hip.h"
 
 using namespace azg;
 
@@ -476,6 +477,25 @@ extern "C" int azg_nn_aba21_forward(const int8_t* boards, const uint8_t* valid, 
         attr = true;
     }
     k_aba21_net<4, 2><<<dim3((B + ABA_NS - 1) / ABA_NS), dim3(ABA_THREADS), ABA_LDS, (hipStream_t)stream>>>(N, boards, valid, B, pi, v);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- Smallworld net V62 (3-layer transformer encoder over the N tokens, P = 2 / 3 / 4): one launch, 4 / 3 / 2 samples per workgroup
+// (nn_smallworld.hip.h) ----
+extern "C" int azg_nn_sw62_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_layers, int A, int P, int B,
+                                   float* pi, float* v, void* stream) {
+    if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_sw62_forward: null/empty argument");
+    if (n_layers != SW_LAYERS || !((P == 2 && A == Sw62<2>::A) || (P == 3 && A == Sw62<3>::A) || (P == 4 && A == Sw62<4>::A)))
+        return fail("azg_nn_sw62_forward: built for 3 layers and (P, A) = (2, 131), (3, 166) or (4, 211)");
+    for (int i = 0; i < SW_NW; i++)
+        if (!w[i]) return fail("azg_nn_sw62_forward: null weight pointer");
+    Sw62NetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], w[15], w[16], w[17], w[18],
+               w[19], w[20], w[21], w[22], w[23], w[24]};
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 2) k_sw62_net<2><<<dim3((B + Sw62<2>::NS - 1) / Sw62<2>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
+    else if (P == 3) k_sw62_net<3><<<dim3((B + Sw62<3>::NS - 1) / Sw62<3>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
+    else k_sw62_net<4><<<dim3((B + Sw62<4>::NS - 1) / Sw62<4>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
     HIPCHK(hipGetLastError());
     return 0;
 }

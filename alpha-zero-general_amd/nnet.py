@@ -1156,6 +1156,177 @@ class AbaloneV21Hip:
         return pi[0].cpu().numpy(), v[0].cpu().numpy()
 
 
+class SmallworldV62:
+    """smallworld/SmallworldNNet.py nn_version 62 (:246-254, stem :86-137, heads :139-180, forward :268-294) -- the net of all three shipped
+    checkpoints (pretrained_{2,3,4}pl.pt): InputStem over the (N, 8) tokens -> 48, three post-norm TransformerEncoderLayers (3 heads of 16,
+    feed-forward 192, ReLU, LayerNorm eps 1e-5, no mask), ActionSlicerHead (local 48 -> 5 on the nA area tokens, mean of the other tokens
+    -> global 48 -> 16 and value 48 -> P), masked softmax, tanh.  The stem's out_proj is linear over the concatenation of its five parts,
+    so it is folded (in f64) into three lookup tables and one 21 -> 48 projection; the 1/4 attention scale is folded into the Q rows of
+    in_proj (exact).  Plain torch ops."""
+    N_TOKENS = {2: 40, 3: 52, 4: 66}
+    _TENSORS = ('t_ppl', 't_pwr', 't_pl', 'w_st', 'b_st', 'ln_s', 'local', 'glob', 'value')
+
+    def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
+        sd = {k: torch.as_tensor(v).double() for k, v in state_dict.items() if not k.endswith('powers_of_2')}
+        self.P, self.N = num_players, self.N_TOKENS[num_players]
+        self.nA = {2: 23, 3: 30, 4: 39}[num_players]
+        self.A = 5 * self.nA + 16
+        assert sd['head.value_head.weight'].shape[0] == num_players
+        wo, bo = sd['stem.out_proj.weight'], sd['stem.out_proj.bias']            # [48][240]: ppl | pwr | player | num | bits
+        sl = [wo[:, 48 * k:48 * (k + 1)] for k in range(5)]
+        self.t_ppl = sd['stem.emb_ppl.weight'] @ sl[0].t()
+        self.t_pwr = sd['stem.emb_pwr.weight'] @ sl[1].t()
+        self.t_pl = sd['stem.emb_player.weight'] @ sl[2].t()
+        self.w_st = torch.cat([(sl[3] @ sd['stem.num_proj.weight']).t(), (sl[4] @ sd['stem.bit_proj.weight']).t()])     # [21][48]
+        self.b_st = bo + sl[3] @ sd['stem.num_proj.bias'] + sl[4] @ sd['stem.bit_proj.bias']
+        self.ln_s = (sd['stem.norm.weight'], sd['stem.norm.bias'])
+        self.layers = []
+        i = 0
+        while 'trunk.layers.%d.linear1.weight' % i in sd:
+            q = lambda n: sd['trunk.layers.%d.%s' % (i, n)]  # noqa: E731
+            scale = torch.ones(144, dtype=torch.float64)
+            scale[:48] = 0.25                                                           # 1 / sqrt(16): a power of two, exact
+            self.layers.append(dict(w_in=q('self_attn.in_proj_weight') * scale[:, None], b_in=q('self_attn.in_proj_bias') * scale,
+                                    w_o=q('self_attn.out_proj.weight'), b_o=q('self_attn.out_proj.bias'),
+                                    ln1=(q('norm1.weight'), q('norm1.bias')), w1=q('linear1.weight'), b1=q('linear1.bias'),
+                                    w2=q('linear2.weight'), b2=q('linear2.bias'), ln2=(q('norm2.weight'), q('norm2.bias'))))
+            i += 1
+        self.local = (sd['head.local_head.weight'], sd['head.local_head.bias'])
+        self.glob = (sd['head.global_head.weight'], sd['head.global_head.bias'])
+        self.value = (sd['head.value_head.weight'], sd['head.value_head.bias'])
+        self.to(device, dtype)
+
+    def to(self, device, dtype=torch.float32):
+        self.device, self.dtype = torch.device(device), dtype
+        mv = lambda t: tuple(mv(x) for x in t) if isinstance(t, tuple) else t.to(self.device, dtype).contiguous()  # noqa: E731
+        for n in self._TENSORS:
+            setattr(self, n, mv(getattr(self, n)))
+        self.layers = [{k: mv(t) for k, t in lay.items()} for lay in self.layers]
+        self.shifts = torch.arange(8, device=self.device)
+        return self
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        z = np.load(path)
+        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        B = boards.shape[0]
+        b = boards.reshape(B, self.N, 8)
+        c = b.to(torch.int64)
+        e1, e2, e7 = (c[..., 1] + 15).clamp(0, 30), (c[..., 2] + 20).clamp(0, 40), (c[..., 7] + 1).clamp(0, 5)
+        num = torch.cat([b[..., 0:1], b[..., 3:7]], dim=-1).to(torch.float32) / 10.0       # (slices, not a list index: no host copy in graph capture)
+        bits = torch.cat([(c[..., 3:4] >> self.shifts) & 1, (c[..., 4:5] >> self.shifts) & 1], dim=-1)   # bits of the two's-complement pattern
+        f = torch.cat([num.to(self.dtype), bits.to(self.dtype)], dim=-1)
+        x = self.t_ppl[e1] + self.t_pwr[e2] + self.t_pl[e7] + f @ self.w_st + self.b_st
+        x = F.layer_norm(x, (48,), *self.ln_s, eps=1e-5)
+        for lay in self.layers:
+            qkv = F.linear(x, lay['w_in'], lay['b_in']).view(B, self.N, 3, 3, 16)                       # (token, q|k|v, head, dim)
+            q, k, v = (qkv[:, :, j].transpose(1, 2) for j in range(3))                                   # [B][head][N][16]
+            o = torch.softmax(q @ k.transpose(-1, -2), dim=-1) @ v
+            o = F.linear(o.transpose(1, 2).reshape(B, self.N, 48), lay['w_o'], lay['b_o'])
+            x = F.layer_norm(x + o, (48,), *lay['ln1'], eps=1e-5)
+            y = F.linear(F.relu(F.linear(x, lay['w1'], lay['b1'])), lay['w2'], lay['b2'])
+            x = F.layer_norm(x + y, (48,), *lay['ln2'], eps=1e-5)
+        nA = self.nA
+        loc = F.linear(x[:, :nA], *self.local)                                                           # [B][nA][5]
+        g = x[:, nA:].mean(dim=1)
+        gl = F.linear(g, *self.glob)
+        logits = torch.cat([loc[..., 0], loc[..., 1], loc[..., 2], loc[..., 3], gl[:, 0:8], loc[..., 4], gl[:, 8:16]], dim=1).float()
+        v = torch.tanh(F.linear(g, *self.value).float())
+        logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
+        return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
+        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+class SmallworldV62Hip:
+    """SmallworldV62 (3 transformer layers, P = 2 / 3 / 4) evaluated by the engine's one-launch kernel (azg_nn_sw62_forward,
+    csrc/nn_smallworld.hip.h: f32 MFMA for the per-token GEMMs and the two attention products, stem / softmax / LayerNorm / heads on
+    the vector ALUs, masked softmax in the same launch) instead of ~40 torch launches.  Wraps a SmallworldV62; static pi / v buffers
+    (HIP-graph capture of the engine's rounds)."""
+
+    def __init__(self, base, max_batch=4096):
+        import ctypes as C
+        from . import _lib
+        self._lib, self.base, self.device = _lib, base, base.device
+        self.P, self.A, self.N = base.P, base.A, base.N
+        assert base.dtype == torch.float32 and self.device.type == 'cuda' and len(base.layers) == 3
+        keep = self.pack(base)
+        self._keep = keep
+        self.ptrs = (C.c_void_p * 25)(*[t.data_ptr() for t in keep])
+        self._alloc(max_batch)
+
+    @staticmethod
+    def frag(wt, nct):
+        """W^T [K][Nout] (K a multiple of 16) -> [nct][K / 4][64 lanes], element [ct][m][lane] = W^T[16 (m >> 2) + 4 (lane >> 4) + (m & 3)]
+        [16 ct + (lane & 15)] (zero padded): the k order of every GEMM of nn_smallworld.hip.h"""
+        K = wt.shape[0]
+        z = torch.zeros((K, 16 * nct), dtype=torch.float32, device=wt.device)
+        z[:, :wt.shape[1]] = wt
+        return z.view(K // 16, 4, 4, nct, 16).permute(3, 0, 2, 1, 4).contiguous().view(-1)
+
+    @staticmethod
+    def pack(base):
+        """the 25 weight tensors of azg_nn_sw62_forward (include/azg.h), on base's device"""
+        fr, L = SmallworldV62Hip.frag, base.layers
+        cat = lambda ts: torch.cat([t.reshape(-1) for t in ts]).contiguous()  # noqa: E731
+        keep = [base.t_ppl, base.t_pwr, base.t_pl, base.w_st, base.b_st, base.ln_s[0], base.ln_s[1],
+                cat([fr(y['w_in'].t(), 9) for y in L]), cat([y['b_in'] for y in L]),
+                cat([fr(y['w_o'].t(), 3) for y in L]), cat([y['b_o'] for y in L]),
+                cat([y['ln1'][0] for y in L]), cat([y['ln1'][1] for y in L]),
+                cat([fr(y['w1'].t(), 12) for y in L]), cat([y['b1'] for y in L]),
+                cat([fr(y['w2'].t(), 3) for y in L]), cat([y['b2'] for y in L]),
+                cat([y['ln2'][0] for y in L]), cat([y['ln2'][1] for y in L]),
+                base.local[0].t().contiguous(), base.local[1], base.glob[0].t().contiguous(), base.glob[1],
+                base.value[0].t().contiguous(), base.value[1]]
+        assert tuple(base.w_st.shape) == (21, 48) and tuple(base.t_ppl.shape) == (31, 48) and tuple(L[0]['w1'].shape) == (192, 48)
+        return [t.to(torch.float32).contiguous() for t in keep]
+
+    def _alloc(self, B):
+        self.maxB = B
+        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+
+    def clone_buffers(self):
+        import copy
+        other = copy.copy(self)
+        other._alloc(self.maxB)
+        return other
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        import ctypes as C
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        boards = boards.reshape(B, -1)
+        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == self.N * 8
+        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+        assert valids.shape == (B, self.A) and valids.is_cuda
+        self._lib.check(self._lib.lib().azg_nn_sw62_forward(p(boards), p(valids), self.ptrs, 3, self.A, self.P, B, p(self.pi), p(self.v),
+                                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self.pi[:B], self.v[:B]
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
 class TorchModuleEvaluator:
     """Leaf evaluator around ANY torch module with the reference's forward signature
     `module(board f32[B, *board_shape], valid_actions bool[B, A]) -> (log_pi f32[B, A], v f32[B, P])` -- the torch branch of

@@ -231,6 +231,67 @@ class AbaloneV21Module(nn.Module):
         pi = torch.where(valid_actions.bool(), pi, self.lowvalue)
         return F.log_softmax(pi, dim=1), torch.tanh(v)
 
+class _SmallworldStem(nn.Module):
+    """smallworld/SmallworldNNet.py InputStem (:86-137) with its parameter names: embeddings of the clamped columns 1, 2, 7, a 5 -> D
+    projection of columns 0, 3..6 / 10, a 16 -> D projection of the 8 low bits of columns 3 and 4, out_proj over the five parts, LayerNorm"""
+
+    def __init__(self, d):
+        super().__init__()
+        self.emb_ppl, self.emb_pwr, self.emb_player = nn.Embedding(31, d), nn.Embedding(41, d), nn.Embedding(6, d)
+        self.num_proj, self.bit_proj = nn.Linear(5, d), nn.Linear(16, d)
+        self.out_proj, self.norm = nn.Linear(5 * d, d), nn.LayerNorm(d)
+        self.register_buffer('powers_of_2', 2 ** torch.arange(8, dtype=torch.long))
+
+    def forward(self, x):
+        c = x.long()
+        e = [self.emb_ppl((c[..., 1] + 15).clamp(0, 30)), self.emb_pwr((c[..., 2] + 20).clamp(0, 40)), self.emb_player((c[..., 7] + 1).clamp(0, 5))]
+        e.append(self.num_proj(torch.cat([x[..., 0:1], x[..., 3:7]], dim=-1).float() / 10.0))
+        bits = torch.cat([torch.div(c[..., j:j + 1], self.powers_of_2, rounding_mode='floor') % 2 for j in (3, 4)], dim=-1)
+        e.append(self.bit_proj(bits.float()))
+        return self.norm(self.out_proj(torch.cat(e, dim=-1)))
+
+
+class _SmallworldHead(nn.Module):
+    """ActionSlicerHead (:139-180): local 48 -> 5 on the nA area tokens, mean of the rest -> global 48 -> 16 and value 48 -> P, in the
+    policy layout [l0 | l1 | l2 | l3 | g0..7 | l4 | g8..15]"""
+
+    def __init__(self, d, action_size, num_players):
+        super().__init__()
+        self.nb_areas = (action_size - 16) // 5
+        self.local_head, self.global_head, self.value_head = nn.Linear(d, 5), nn.Linear(d, 16), nn.Linear(d, num_players)
+
+    def forward(self, x):
+        loc = self.local_head(x[:, :self.nb_areas])
+        g = x[:, self.nb_areas:].mean(dim=1)
+        gl = self.global_head(g)
+        pi = torch.cat([loc[..., 0], loc[..., 1], loc[..., 2], loc[..., 3], gl[:, :8], loc[..., 4], gl[:, 8:]], dim=1)
+        return pi, self.value_head(g)
+
+
+class SmallworldV62Module(nn.Module):
+    """smallworld/SmallworldNNet.py nn_version 62 (:246-254, forward :268-294; pretrained_{2,3,4}pl.pt) with the reference's parameter and
+    buffer names: stem.*, three nn.TransformerEncoderLayer (d_model 48, 3 heads, feed-forward 192, post-norm) as trunk.layers.N.*, head.*,
+    lowvalue.  In training mode the stem output goes through dropout when dropout > 0, and the encoder layers apply their own dropouts."""
+    version = 62
+    N_TOKENS = {2: 40, 3: 52, 4: 66}
+
+    def __init__(self, num_players=2, action_size=131, dropout=0.0):
+        super().__init__()
+        self.P, self.A, self.dropout, self.N = num_players, action_size, dropout, self.N_TOKENS[num_players]
+        self.stem = _SmallworldStem(48)
+        self.head = _SmallworldHead(48, action_size, num_players)
+        layer = nn.TransformerEncoderLayer(d_model=48, nhead=3, dim_feedforward=192, dropout=dropout, batch_first=True)
+        self.trunk = nn.TransformerEncoder(layer, num_layers=3, enable_nested_tensor=False)
+        self.register_buffer('lowvalue', torch.FloatTensor([-1e8]))
+
+    def forward(self, boards, valid_actions):
+        x = self.stem(boards.reshape(-1, self.N, 8))
+        if self.training and self.dropout > 0:
+            x = F.dropout(x, p=self.dropout)
+        pi, v = self.head(self.trunk(x))
+        pi = torch.where(valid_actions.bool(), pi, self.lowvalue)
+        return F.log_softmax(pi, dim=1), torch.tanh(v)
+
 
 def loss_pi(target_pi, out_log_pi):                                            # GenericNNetWrapper.py:179-181
     return F.kl_div(out_log_pi, target_pi, reduction='batchmean')

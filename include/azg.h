@@ -451,6 +451,23 @@ int azg_nn_s78_forward_h2(const int8_t* boards_dev, const uint8_t* valid_dev, co
    f32 MFMA operands: the full f32 range, same 1e-5 contract as the torch net.  n_blocks must be 4, A 3402, P 2. */
 int azg_nn_aba21_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_blocks, int A, int P, int B,
                          float* pi_dev, float* v_dev, void* stream);
+/* The Smallworld net (nn_version 62, smallworld/SmallworldNNet.py:86-180,246-254,268-294; a 3-layer transformer encoder, d_model 48,
+   3 heads, feed-forward 192): ONE launch on `stream`, 4 / 3 / 2 samples per workgroup for P = 2 / 3 / 4 (nn_smallworld.hip.h).
+   boards int8 [B][N][8] (N = 40 / 52 / 66 tokens), valid u8 [B][A] -> pi f32 [B][A] (masked softmax, A = 5*nA + 16, nA = 23 / 30 / 39
+   area tokens), v f32 [B][P] (tanh).  w = 25 device pointers, f32, L = 3 layers; "frag" = MFMA A-operand fragments of W^T [K][Nout],
+   element [ct][m][lane] = W^T[16*(m>>2) + 4*(lane>>4) + (m&3)][16*ct + (lane&15)]:
+     Tppl [31][48], Tpwr [41][48], Tpl [6][48]   the three embeddings times their out_proj slices (emb @ Wout[:, slice]^T)
+     Wst [21][48], bst [48]                       num_proj and bit_proj folded through out_proj: rows x0, x3, x4, x5, x6 (/ 10), bits 0..7
+                                                  of x3, bits 0..7 of x4; bias = out_proj.bias + out_proj slices of the two biases
+     lnsw, lnsb [48]                              the stem LayerNorm
+     Wqkv [L][9][12][64] frag of in_proj_weight^T with the Q columns * 1/4, bqkv [L][144] (Q part * 1/4)
+     Wo [L][3][12][64] frag of out_proj, bo [L][48]; ln1w, ln1b [L][48]
+     W1 [L][12][12][64] frag of linear1, b1 [L][192]; W2 [L][3][48][64] frag of linear2, b2 [L][48]; ln2w, ln2b [L][48]
+     Wl [48][5], bl [5] local head; Wg [48][16], bg [16] global head; Wv [48][P], bv [P] value head.
+   f32 MFMA operands: the full f32 range, same 1e-5 contract as the torch net.  n_layers must be 3, (P, A) one of (2, 131), (3, 166),
+   (4, 211). */
+int azg_nn_sw62_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_layers, int A, int P, int B,
+                        float* pi_dev, float* v_dev, void* stream);
 /* boards int8 [B][C][7] (reference board layout) -> x f32 [B][7][C] */
 int azg_nn_board_to_x(const int8_t* boards_dev, float* x_dev, int B, int C, void* stream);
 /* boards int8 [B][C][L] -> x f32 [B][L][ldx], columns C..ldx-1 zeroed (row stride padded to a multiple of 4 floats) */

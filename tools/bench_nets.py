@@ -1,5 +1,5 @@
-"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets and the Abalone net (HIP events,
-50 forwards after warm-up)."""
+"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets, the Abalone net and the Smallworld
+nets (HIP events, 50 forwards after warm-up)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -65,3 +65,18 @@ mod.load_state_dict({k[3:]: torch.as_tensor(z[k]) for k in z.files if k.startswi
 print('abalone V21 T=%d' % T, 'torch ops (MIOpen) %.1f us' % timed(base, boards, valids.bool(), 10),
       ' k_aba21_net %.1f us' % timed(nnet.AbaloneV21Hip(base, max_batch=T), boards, valids),
       ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.AbaloneGame()), boards, valids, 10), flush=True)
+
+# Smallworld V62 at T for 2, 3 and 4 players: the plain-torch net (stem folded), the one-launch kernel, and the trainable module through
+# TorchModuleEvaluator (the path of a game without an engine net: nn.TransformerEncoder, log_softmax + exp)
+for P, tag in ((2, 'smallworld_v62'), (3, 'smallworld3_v62'), (4, 'smallworld4_v62')):
+    base = nnet.SmallworldV62.from_npz(G + '/weights_%s.npz' % tag, num_players=P, device='cuda:0')
+    d = np.load(G + '/netfwd_%s.npz' % tag)
+    idx = np.arange(T) % len(d['boards'])
+    boards = torch.from_numpy(d['boards'][idx].reshape(T, -1)).to('cuda:0')
+    valids = torch.from_numpy(d['masks'][idx]).to('cuda:0')
+    z = np.load(G + '/weights_%s.npz' % tag)
+    mod = train.SmallworldV62Module(P, base.A)
+    mod.load_state_dict({k[3:]: torch.as_tensor(z[k]) for k in z.files if k.startswith('sd/')}, strict=True)
+    print('smallworld%d V62 T=%d' % (P, T), 'torch ops %.1f us' % timed(base, boards, valids.bool(), 10),
+          ' k_sw62_net %.1f us' % timed(nnet.SmallworldV62Hip(base, max_batch=T), boards, valids),
+          ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.SmallworldGame(P)), boards, valids, 10), flush=True)

@@ -59,6 +59,11 @@ def forward_f64(name, ckpt_rel, load_kw):
     H.load_reference(**load_kw)
     ck = torch.load(os.path.join(H.REFERENCE, ckpt_rel), map_location='cpu', weights_only=False)
     model = ck['full_model'].eval().double()
+    if hasattr(model, 'stem'):
+        # SmallworldNNet.py InputStem.forward hard-codes .float() on the num_proj / bit_proj inputs: recast them to f64 on the way
+        # in (forward pre-hooks; the reference's source stays as it is)
+        for mod in (model.stem.num_proj, model.stem.bit_proj):
+            mod.register_forward_pre_hook(lambda _m, args: tuple(a.double() for a in args))
     d = np.load(os.path.join(GOLDEN, 'netfwd_%s.npz' % name))
     with torch.no_grad():
         lp, v = model(torch.from_numpy(d['boards'].astype(np.float64)), torch.from_numpy(d['masks'].astype(bool)))
@@ -78,6 +83,9 @@ def main():
         forward_f64('minivilles2_v82', 'minivilles/pretrained_2players.pt', dict(minivilles_players=2))
         forward_f64('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3))
         forward_f64('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict())
+        forward_f64('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2))
+        forward_f64('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3))
+        forward_f64('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4))
         return
     if len(sys.argv) > 2 and sys.argv[1] == '--only':
         return convert(*{'santorini11_v78': ('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11),
@@ -89,7 +97,15 @@ def main():
                          'tlp3_v83': ('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3), 'TLPGame', 'TLPGame', 128),
                          # AbaloneNNet.py nn_version 21 (Belgian Daisy, the layout the engine plays): a 2-d MobileNet on the 9 x 9 grid,
                          # torchvision InvertedResidual blocks (the refshim stand-in); engine net through nn_abalone.hip.h
-                         'abalone_v21': ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict(), 'AbaloneGame', 'AbaloneGame', 128)}[sys.argv[2]])
+                         'abalone_v21': ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict(), 'AbaloneGame', 'AbaloneGame', 128),
+                         # SmallworldNNet.py nn_version 62 (all three shipped checkpoints): a 3-layer transformer encoder over the
+                         # (N, 8) tokens; engine net through nn_smallworld.hip.h
+                         'smallworld_v62': ('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2), 'SmallworldGame',
+                                            'SmallworldGame', 128),
+                         'smallworld3_v62': ('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3), 'SmallworldGame',
+                                             'SmallworldGame', 128),
+                         'smallworld4_v62': ('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4), 'SmallworldGame',
+                                             'SmallworldGame', 128)}[sys.argv[2]])
     convert('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_players=2), 'SplendorGame', 'SplendorGame')
     convert('splendor4_v80', 'splendor/pretrained_4players.pt', dict(splendor_players=4), 'SplendorGame', 'SplendorGame', n_vec=128)
     convert('santorini1_v89', 'santorini/pretrained.pt', dict(santorini_gods=1), 'SantoriniGame', 'SantoriniGame', n_vec=128)
