@@ -19,6 +19,7 @@
 #include "nn_conv5x5.hip.h"
 #include "nn_abalone.hip.h"
 #include "nn_smallworld.hip.h"
+#include "nn_akropolis.hip.h"
 
 using namespace azg;
 
@@ -496,6 +497,23 @@ extern "C" int azg_nn_sw62_forward(const int8_t* boards, const uint8_t* valid, c
     if (P == 2) k_sw62_net<2><<<dim3((B + Sw62<2>::NS - 1) / Sw62<2>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
     else if (P == 3) k_sw62_net<3><<<dim3((B + Sw62<3>::NS - 1) / Sw62<3>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
     else k_sw62_net<4><<<dim3((B + Sw62<4>::NS - 1) / Sw62<4>::NS), dim3(SW_THREADS), 0, st>>>(N, boards, valid, B, pi, v);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- Akropolis net V31 (board convolutions per player + kernel-1 InvertedResidual + bilinear policy per site tile, P = 2 / 3 / 4): one
+// launch, one sample per workgroup (nn_akropolis.hip.h) ----
+extern "C" int azg_nn_akr31_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int P, int A, int B, float* pi,
+                                    float* v, void* stream) {
+    if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_akr31_forward: null/empty argument");
+    if (!((P == 2 && A == Akr31<2>::A) || (P == 3 && A == Akr31<3>::A) || (P == 4 && A == Akr31<4>::A)))
+        return fail("azg_nn_akr31_forward: built for (P, A) = (2, 4056), (3, 5070) or (4, 6084)");
+    for (int i = 0; i < AKR_NW; i++)
+        if (!w[i]) return fail("azg_nn_akr31_forward: null weight pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (P == 2) k_akr31_net<2><<<dim3(B), dim3(AKR_THREADS), 0, st>>>(w[0], w[1], w[2], boards, valid, pi, v);
+    else if (P == 3) k_akr31_net<3><<<dim3(B), dim3(AKR_THREADS), 0, st>>>(w[0], w[1], w[2], boards, valid, pi, v);
+    else k_akr31_net<4><<<dim3(B), dim3(AKR_THREADS), 0, st>>>(w[0], w[1], w[2], boards, valid, pi, v);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -1327,6 +1327,213 @@ class SmallworldV62Hip:
         return pi[0].cpu().numpy(), v[0].cpu().numpy()
 
 
+class AkropolisV31:
+    """akropolis/AkropolisNNet.py nn_version 31 (constructor :91-146, input slicing :377-388, forward :573-622) -- the net of all three
+    shipped checkpoints (pretrained_{2,3,4}pl.pt).  Per player, the board [embed(descr) (3), height, tileID] -> conv3x3(5->8) + BN +
+    Hardswish -> conv3x3(8->8) + BN + Hardswish on 13 x 13 (shared weights); s1 = Linear(15P->16)(scores), g1 = Hardswish(BN(Linear(2->8)
+    (globals))); proj_p = a kernel-1 InvertedResidual (8P + 24 -> 32, depthwise scale, SE 32->8->32, -> 16, no residual) over the cells;
+    per construction-site tile c: t = Hardswish(Conv1d(3->32, k 3)(embed(codes))), f3 = [t, s1, g1], a = Hardswish(BN(proj_i(f3))),
+    h = proj_o(f3) as [6][16]; logit[c, cell, o] = sum_r a[c,r] p[cell,r] h[c,o,r] (action c*1014 + cell*6 + o); masked softmax; value
+    head on flatten(f3).  Every BatchNorm (eps 1e-5) folded; the s1 / g1 channels of proj_p's first 1x1 are constant over the cells and
+    folded into one per-sample 32-vector; the policy is one (169 x 16) x (16 x 6 CS) product per sample with W_c[o][r] = a[c,r] h[c,o,r]
+    (einsum: the reference's (N, CS, 6, 13, 13, 16) product is never formed).  Plain torch ops."""
+    _TENSORS = ('embed', 'w1', 'b1', 'w2', 'b2', 'ws', 'bs', 'wg', 'bg', 'wc', 'bc', 'we', 'wec', 'be', 'dws', 'dwb', 'fc1', 'fc1b', 'fc2',
+                'fc2b', 'wp', 'bp', 'wi', 'bi', 'wo', 'bo', 'wv1', 'bv1', 'wv2', 'bv2', 'wv3', 'bv3')
+
+    def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
+        sd = {k: torch.as_tensor(v).double() for k, v in state_dict.items() if not k.endswith('num_batches_tracked')}
+        P = self.P = num_players
+        self.C, self.CS = 3 * P + 2, P + 2
+        self.S, self.A = 169 * self.C, 1014 * self.CS
+        assert sd['final_layers_V.6.weight'].shape[0] == P and sd['dense_scores.0.weight'].shape[1] == 15 * P
+
+        def conv_bn(conv, bn, bias=True):
+            s, b = _fold_bn(sd, bn)
+            w = sd[conv + '.weight']
+            return w * s.view((-1,) + (1,) * (w.dim() - 1)), (sd[conv + '.bias'] * s if bias else 0) + b
+        self.embed = sd['embed.weight']                                                     # [12][3]
+        self.w1, self.b1 = conv_bn('conv2d_boards.0', 'conv2d_boards.1')                    # [8][5][3][3]
+        self.w2, self.b2 = conv_bn('conv2d_boards.3', 'conv2d_boards.4')                    # [8][8][3][3]
+        self.ws, self.bs = sd['dense_scores.0.weight'].t(), sd['dense_scores.0.bias']       # [15P][16]
+        wg, self.bg = conv_bn('dense_globs.0', 'dense_globs.1')
+        self.wg = wg.t()                                                                    # [2][8]
+        self.wc, self.bc = sd['conv1d_constr.0.weight'], sd['conv1d_constr.0.bias']        # [32][3][3] (out, emb, position)
+        w0, b0 = conv_bn('proj_p.0.block.0.0', 'proj_p.0.block.0.1', bias=False)
+        w0 = w0.reshape(32, 8 * P + 24)
+        self.we, self.wec, self.be = w0[:, :8 * P].t(), w0[:, 8 * P:].t(), b0              # [8P][32], [24][32] (s1 | g1), [32]
+        dw, self.dwb = conv_bn('proj_p.0.block.1.0', 'proj_p.0.block.1.1', bias=False)
+        self.dws = dw.reshape(32)                                                           # the depthwise 1x1: a per-channel scale
+        self.fc1, self.fc1b = sd['proj_p.0.block.2.fc1.weight'].reshape(8, 32).t(), sd['proj_p.0.block.2.fc1.bias']
+        self.fc2, self.fc2b = sd['proj_p.0.block.2.fc2.weight'].reshape(32, 8).t(), sd['proj_p.0.block.2.fc2.bias']
+        wp, self.bp = conv_bn('proj_p.0.block.3.0', 'proj_p.0.block.3.1', bias=False)
+        self.wp = wp.reshape(16, 32).t()                                                    # [32][16]
+        wi, self.bi = conv_bn('proj_i', 'b1n.0')                                            # b1n folded into proj_i
+        self.wi = wi.t()                                                                    # [56][16]
+        self.wo, self.bo = sd['proj_o.weight'].t(), sd['proj_o.bias']                      # [56][96]: h[o][r] = column 16 o + r
+        wv1, self.bv1 = conv_bn('final_layers_V.1', 'final_layers_V.2')
+        self.wv1 = wv1.t()                                                                  # [CS * 56][16]
+        self.wv2, self.bv2 = sd['final_layers_V.4.weight'].t(), sd['final_layers_V.4.bias']
+        self.wv3, self.bv3 = sd['final_layers_V.6.weight'].t(), sd['final_layers_V.6.bias']
+        self.to(device, dtype)
+
+    def to(self, device, dtype=torch.float32):
+        self.device, self.dtype = torch.device(device), dtype
+        for n in self._TENSORS:
+            setattr(self, n, getattr(self, n).to(self.device, dtype).contiguous())
+        return self
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        z = np.load(path)
+        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
+
+    def context(self, x):
+        """x [B][13][13][C] (self.dtype) -> s1 [B][16], g1 [B][8], f3 [B][CS][56]"""
+        P, CS = self.P, self.CS
+        B = x.shape[0]
+        s1 = x[:, 0:3 * P, 0:5, 3 * P].reshape(B, 15 * P) @ self.ws + self.bs
+        g1 = F.hardswish(x[:, CS + 1, 0:2, 3 * P + 1] @ self.wg + self.bg)
+        ce = self.embed[x[:, 0:CS, 0:3, 3 * P + 1].clamp(0, 11).long()]                   # [B][CS][3 positions][3]
+        t = F.hardswish(torch.einsum('bcke,oek->bco', ce, self.wc) + self.bc)
+        f3 = torch.cat([t, s1[:, None].expand(B, CS, 16), g1[:, None].expand(B, CS, 8)], dim=2)
+        return s1, g1, f3
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        P, CS = self.P, self.CS
+        B = boards.shape[0]
+        x = boards.reshape(B, 13, 13, self.C).to(self.dtype)
+        s1, g1, f3 = self.context(x)
+        # the P boards, shared convolutions: [B * P][5][13][13]
+        e = self.embed[x[..., 0:P].clamp(0, 11).long()]                                     # [B][13][13][P][3]
+        xb = torch.cat([e, x[..., P:2 * P, None], x[..., 2 * P:3 * P, None]], dim=4)       # [B][13][13][P][5]
+        xb = xb.permute(0, 3, 4, 1, 2).reshape(B * P, 5, 13, 13)
+        hb = F.hardswish(F.conv2d(xb, self.w1, self.b1, padding=1))
+        hb = F.hardswish(F.conv2d(hb, self.w2, self.b2, padding=1))                        # [B * P][8][13][13]
+        fb = hb.reshape(B, P * 8, 169).transpose(1, 2)                                      # [B][169][8P], channel 8 i + k of player i
+        c0 = torch.cat([s1, g1], dim=1) @ self.wec + self.be                               # proj_p's s1 / g1 channels: one 32-vector per sample
+        d = F.hardswish(F.hardswish(fb @ self.we + c0[:, None]) * self.dws + self.dwb)      # [B][169][32]
+        sc = F.hardsigmoid(F.relu(d.mean(dim=1) @ self.fc1 + self.fc1b) @ self.fc2 + self.fc2b)
+        p = (d * sc[:, None]) @ self.wp + self.bp                                           # [B][169][16]
+        a = F.hardswish(f3 @ self.wi + self.bi)                                             # [B][CS][16]
+        wc = a[:, :, None, :] * (f3 @ self.wo + self.bo).view(B, CS, 6, 16)               # W_c [B][CS][6][16]
+        logits = torch.einsum('bnr,bcor->bcno', p, wc).reshape(B, self.A).float()
+        v = F.hardswish(f3.reshape(B, CS * 56) @ self.wv1 + self.bv1)
+        v = torch.tanh((F.hardswish(v @ self.wv2 + self.bv2) @ self.wv3 + self.bv3).float())
+        logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
+        return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
+        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+class AkropolisV31Hip:
+    """AkropolisV31 (P = 2 / 3 / 4) evaluated by the engine's one-launch kernel (azg_nn_akr31_forward, csrc/nn_akropolis.hip.h: one
+    workgroup per sample, one cell per lane, the whole forward and the masked softmax on the vector ALUs) instead of ~50 torch
+    launches.  Wraps an AkropolisV31; static pi / v buffers (HIP-graph capture of the engine's rounds)."""
+
+    @staticmethod
+    def layout(P):
+        """the three packed weight blocks of azg_nn_akr31_forward (include/azg.h, Akr31<P> offsets in nn_akropolis.hip.h): per block
+        the (name, shape) of its tensors in order"""
+        CS = P + 2
+        return ([('ws', (15 * P, 16)), ('bs', (16,)), ('wg', (2, 8)), ('bg', (8,)), ('tc', (3, 12, 32)), ('bc', (32,)), ('wi', (56, 16)),
+                 ('bi', (16,)), ('wo', (56, 96)), ('bo', (96,)), ('wec', (24, 32)), ('be', (32,)), ('wv1', (56 * CS, 16)), ('bv1', (16,)),
+                 ('wv2', (16, 16)), ('bv2', (16,)), ('wv3', (16, P)), ('bv3', (P,))],
+                [('t1', (9, 12, 8)), ('w1x', (9, 2, 8)), ('b1', (8,)), ('w2', (9, 8, 8)), ('b2', (8,)), ('we', (8 * P, 32))],
+                [('dws', (32,)), ('dwb', (32,)), ('fc1', (32, 8)), ('fc1b', (8,)), ('fc2', (8, 32)), ('fc2b', (32,)), ('wp', (32, 16)),
+                 ('bp', (16,))])
+
+    @staticmethod
+    def folded(base):
+        """name -> tensor of every operand the kernel reads, in base's dtype: base's folds plus the embedding folded into the per-tap
+        code tables of conv1 (t1) and the per-position code tables of conv1d_constr (tc)"""
+        w1 = base.w1.permute(2, 3, 1, 0).reshape(9, 5, 8)                                  # [tap = 3 ky + kx][in][out]
+        f = {n: getattr(base, n) for n in ('ws', 'bs', 'wg', 'bg', 'bc', 'wi', 'bi', 'wo', 'bo', 'wec', 'be', 'wv1', 'bv1', 'wv2', 'bv2',
+                                           'wv3', 'bv3', 'b1', 'b2', 'we', 'dws', 'dwb', 'fc1', 'fc1b', 'fc2', 'fc2b', 'wp', 'bp')}
+        f['t1'] = torch.einsum('ce,teo->tco', base.embed, w1[:, 0:3])                       # [9][12][8]: embed(code) through tap t
+        f['w1x'] = w1[:, 3:5]                                                                # [9][2][8]: height, tileID
+        f['w2'] = base.w2.permute(2, 3, 1, 0).reshape(9, 8, 8)                              # [tap][in][out]
+        f['tc'] = torch.einsum('ce,oek->kco', base.embed, base.wc)                          # [3][12][32]: embed(code) at position k
+        return f
+
+    @staticmethod
+    def pack(base):
+        """the three f32 weight blocks of azg_nn_akr31_forward, on base's device"""
+        f = AkropolisV31Hip.folded(base)
+        blocks = []
+        for blk in AkropolisV31Hip.layout(base.P):
+            for n, shape in blk:
+                assert tuple(f[n].shape) == shape, (n, tuple(f[n].shape), shape)
+            blocks.append(torch.cat([f[n].reshape(-1) for n, _ in blk]).to(torch.float32).contiguous())
+        return blocks
+
+    @staticmethod
+    def unpack(blocks, P):
+        """inverse of pack: name -> tensor view"""
+        out = {}
+        for blk, t in zip(AkropolisV31Hip.layout(P), blocks):
+            o = 0
+            for n, shape in blk:
+                k = int(np.prod(shape))
+                out[n] = t[o:o + k].view(shape)
+                o += k
+            assert o == t.numel()
+        return out
+
+    def __init__(self, base, max_batch=4096):
+        import ctypes as C
+        from . import _lib
+        self._lib, self.base, self.device = _lib, base, base.device
+        self.P, self.A, self.S = base.P, base.A, base.S
+        assert base.dtype == torch.float32 and self.device.type == 'cuda'
+        keep = self.pack(base)
+        self._keep = keep
+        self.ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in keep])
+        self._alloc(max_batch)
+
+    def _alloc(self, B):
+        self.maxB = B
+        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+
+    def clone_buffers(self):
+        import copy
+        other = copy.copy(self)
+        other._alloc(self.maxB)
+        return other
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        import ctypes as C
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        boards = boards.reshape(B, -1)
+        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == self.S
+        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+        assert valids.shape == (B, self.A) and valids.is_cuda
+        self._lib.check(self._lib.lib().azg_nn_akr31_forward(p(boards), p(valids), self.ptrs, self.P, self.A, B, p(self.pi), p(self.v),
+                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self.pi[:B], self.v[:B]
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
 class TorchModuleEvaluator:
     """Leaf evaluator around ANY torch module with the reference's forward signature
     `module(board f32[B, *board_shape], valid_actions bool[B, A]) -> (log_pi f32[B, A], v f32[B, P])` -- the torch branch of

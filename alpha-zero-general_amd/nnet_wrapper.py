@@ -24,7 +24,7 @@ import torch
 from . import _lib, nnet as _nn, train as _train
 
 # nn_version -> trainable module per game (splendor/SplendorNNet.py V80, azul/AzulNNet.py V84, santorini/SantoriniNNet.py V89/V78,
-# abalone/AbaloneNNet.py V21, smallworld/SmallworldNNet.py V62)
+# abalone/AbaloneNNet.py V21, smallworld/SmallworldNNet.py V62, akropolis/AkropolisNNet.py V31)
 _DEFAULT_VERSION = {(_lib.SPLENDOR, 2): 80, (_lib.SPLENDOR, 3): 80, (_lib.SPLENDOR, 4): 80, (_lib.AZUL, 2): 84,
                     (_lib.SANTORINI, 1): 89, (_lib.SANTORINI, 11): 78}
 
@@ -43,8 +43,10 @@ def _module_for(game, version, dropout):
         return _train.AbaloneV21Module(P, A, dropout)
     if gid == _lib.SMALLWORLD and version == 62:
         return _train.SmallworldV62Module(P, A, dropout)
+    if gid == _lib.AKROPOLIS and version == 31:
+        return _train.AkropolisV31Module(P, A, dropout)
     raise ValueError('nn_version %r is not built for this game (engine nets: Splendor 80, Azul 84, Santorini 89 no-gods / 78 with gods, '
-                     'Abalone 21, Smallworld 62)'
+                     'Abalone 21, Smallworld 62, Akropolis 31)'
                      % (version,))
 
 
@@ -53,8 +55,10 @@ def evaluator_for(module, game, max_batch):
     sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
     dev, ver = str(game.device), getattr(module, 'version', 80)
     if not isinstance(module, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
-                               _train.AbaloneV21Module, _train.SmallworldV62Module)):
+                               _train.AbaloneV21Module, _train.SmallworldV62Module, _train.AkropolisV31Module)):
         return _nn.TorchModuleEvaluator(module, game, max_batch)
+    if ver == 31:
+        return _nn.AkropolisV31Hip(_nn.AkropolisV31(sd, num_players=game.P, device=dev), max_batch=max_batch)
     if ver == 62:
         return _nn.SmallworldV62Hip(_nn.SmallworldV62(sd, num_players=game.P, device=dev), max_batch=max_batch)
     if ver == 21:

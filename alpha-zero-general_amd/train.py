@@ -292,6 +292,82 @@ class SmallworldV62Module(nn.Module):
         pi = torch.where(valid_actions.bool(), pi, self.lowvalue)
         return F.log_softmax(pi, dim=1), torch.tanh(v)
 
+class _SqueezeExcitation2d(nn.Module):
+    """torchvision's SqueezeExcitation: mean over the cells, fc1 (1x1 conv) + ReLU, fc2 (1x1 conv) + Hardsigmoid, scale"""
+
+    def __init__(self, c, squeeze):
+        super().__init__()
+        self.fc1, self.fc2 = nn.Conv2d(c, squeeze, 1), nn.Conv2d(squeeze, c, 1)
+
+    def forward(self, x):
+        return x * F.hardsigmoid(self.fc2(F.relu(self.fc1(F.adaptive_avg_pool2d(x, 1)))))
+
+
+class _MBBlockSE1x1(nn.Module):
+    """torchvision's MobileNetV3 InvertedResidual with kernel 1, SE and Hardswish, as AkropolisNNet.py:136 configures `proj_p`
+    (8P + 24 -> 32 -> 16): expand 1x1 + BN + Hardswish, depthwise 1x1 + BN + Hardswish, SE (squeeze 8), project 1x1 + BN; the residual
+    only when in == out channels.  Parameter names block.{0,1,3}.{0 conv, 1 BatchNorm}, block.2.fc{1,2}"""
+
+    def __init__(self, c_in, e, c_out):
+        super().__init__()
+        cna = lambda i, o, g, act: nn.Sequential(nn.Conv2d(i, o, 1, groups=g, bias=False), nn.BatchNorm2d(o),  # noqa: E731
+                                                 *([nn.Hardswish()] if act else []))
+        self.block = nn.Sequential(cna(c_in, e, 1, True), cna(e, e, e, True), _SqueezeExcitation2d(e, _make_divisible(e // 4, 8)),
+                                   cna(e, c_out, 1, False))
+        self.use_res_connect = c_in == c_out
+
+    def forward(self, x):
+        y = self.block(x)
+        return y + x if self.use_res_connect else y
+
+
+class AkropolisV31Module(nn.Module):
+    """akropolis/AkropolisNNet.py nn_version 31 (constructor :91-146, forward :377-388,573-622; pretrained_{2,3,4}pl.pt) with the
+    reference's parameter names: embed, conv1d_constr, dense_scores, conv2d_boards, dense_globs, final_layers_V, proj_i, proj_p, proj_o,
+    b1n, lowvalue.  In training mode s1, g1 and the conv1d output go through dropout, as in the reference."""
+    version = 31
+
+    def __init__(self, num_players=2, action_size=4056, dropout=0.0):
+        super().__init__()
+        P = num_players
+        self.P, self.A, self.dropout, self.CS = P, action_size, dropout, P + 2
+        D, T, S, G, B, r = 3, 32, 16, 8, 8, 16
+        self.embed = nn.Embedding(12, D)
+        self.conv1d_constr = nn.Sequential(nn.Conv1d(D, T, kernel_size=3), nn.Hardswish())
+        self.dense_scores = nn.Sequential(nn.Linear(15 * P, S))
+        self.conv2d_boards = nn.Sequential(nn.Conv2d(D + 2, B, 3, padding=1), nn.BatchNorm2d(B), nn.Hardswish(),
+                                           nn.Conv2d(B, B, 3, padding=1), nn.BatchNorm2d(B), nn.Hardswish())
+        self.dense_globs = nn.Sequential(nn.Linear(2, G), nn.BatchNorm1d(G), nn.Hardswish())
+        self.final_layers_V = nn.Sequential(nn.Flatten(1), nn.Linear(self.CS * (T + S + G), r), nn.BatchNorm1d(r), nn.Hardswish(),
+                                            nn.Linear(r, r), nn.Hardswish(), nn.Linear(r, P))
+        self.proj_i = nn.Linear(T + S + G, r)
+        self.proj_p = nn.Sequential(_MBBlockSE1x1(P * B + G + S, 2 * r, r))
+        self.proj_o = nn.Linear(T + G + S, 6 * r)
+        self.b1n = nn.Sequential(nn.BatchNorm1d(r), nn.Hardswish())
+        self.register_buffer('lowvalue', torch.FloatTensor([-1e8]))
+
+    def forward(self, boards, valid_actions):
+        P, CS = self.P, self.CS
+        x = boards.reshape(-1, 13, 13, 3 * P + 2).float().permute(0, 3, 1, 2)
+        N = x.shape[0]
+        drop = lambda t: F.dropout(t, p=self.dropout, training=self.training)  # noqa: E731
+        s1 = drop(self.dense_scores(x[:, 3 * P, :3 * P, :5].flatten(1)))
+        g1 = drop(self.dense_globs(x[:, 3 * P + 1, CS + 1, :2]))
+        descr = self.embed(x[:, :P].clamp(0, 11).long())                                  # N, P, 13, 13, D
+        bx = torch.cat([descr, x[:, P:2 * P, ..., None], x[:, 2 * P:3 * P, ..., None]], dim=-1)
+        bf = [self.conv2d_boards(bx[:, i].permute(0, 3, 1, 2)) for i in range(P)]
+        fused_4d = torch.cat(bf + [s1[..., None, None].expand(-1, -1, 13, 13), g1[..., None, None].expand(-1, -1, 13, 13)], dim=1)
+        ce = self.embed(x[:, 3 * P + 1, :CS, :3].clamp(0, 11).long())                      # N, CS, 3, D
+        t = drop(self.conv1d_constr(ce.flatten(0, 1).permute(0, 2, 1))).view(N, CS, -1)
+        f3 = torch.cat([t, s1[:, None].expand(-1, CS, -1), g1[:, None].expand(-1, CS, -1)], dim=-1)
+        a = self.b1n(self.proj_i(f3).permute(0, 2, 1)).permute(0, 2, 1)                  # N, CS, r
+        p = self.proj_p(fused_4d).flatten(2)                                                # N, r, 169
+        h = self.proj_o(f3).view(N, CS, 6, -1)                                              # N, CS, 6, r
+        pi = torch.einsum('nrk,ncor->ncko', p, a[:, :, None] * h).flatten(1)                # (the reference's 6-d product, summed over r)
+        pi = torch.where(valid_actions.bool(), pi, self.lowvalue)
+        v = self.final_layers_V(f3)
+        return F.log_softmax(pi, dim=1), torch.tanh(v)
+
 
 def loss_pi(target_pi, out_log_pi):                                            # GenericNNetWrapper.py:179-181
     return F.kl_div(out_log_pi, target_pi, reduction='batchmean')

@@ -468,6 +468,20 @@ int azg_nn_aba21_forward(const int8_t* boards_dev, const uint8_t* valid_dev, con
    (4, 211). */
 int azg_nn_sw62_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_layers, int A, int P, int B,
                         float* pi_dev, float* v_dev, void* stream);
+/* The Akropolis net (nn_version 31, akropolis/AkropolisNNet.py:91-146,377-388,573-622; pretrained_{2,3,4}pl.pt): ONE launch on `stream`,
+   one sample per workgroup of 192 threads (nn_akropolis.hip.h).  boards int8 [B][13][13][3P + 2], valid u8 [B][A] -> pi f32 [B][A]
+   (masked softmax, A = 1014 (P + 2), action c*1014 + cell*6 + o), v f32 [B][P] (tanh).  w = 3 device pointers to packed f32 blocks,
+   tensors back to back in this order (every BatchNorm folded into the layer before it; CS = P + 2):
+     w[0]  Ws [15P][16], bs [16] (dense_scores^T); Wg [2][8], bg [8] (dense_globs); Tc [3][12][32] (embedding through conv1d_constr, per
+           position and code), bc [32]; Wi [56][16], bi [16] (proj_i with b1n); Wo [56][96], bo [96] (proj_o^T); Wec [24][32], be [32]
+           (proj_p's first 1x1 on the s1 | g1 channels, + its BN shift); Wv1 [56 CS][16], bv1 [16], Wv2 [16][16], bv2 [16], Wv3 [16][P],
+           bv3 [P] (value head)
+     w[1]  T1 [9 taps][12 codes][8] (embedding through conv1), W1x [9][2][8] (conv1's height / tileID columns), b1 [8]; W2 [9][8 in][8 out],
+           b2 [8] (conv2); We [8P][32] (proj_p's first 1x1 on the board channels, player-major)
+     w[2]  dws, dwb [32] (depthwise 1x1 + BN), fc1 [32][8], fc1b [8], fc2 [8][32], fc2b [32] (SE), Wp [32][16], bp [16] (project)
+   f32 operands, f32 accumulation (the policy dot products in f64).  (P, A) must be (2, 4056), (3, 5070) or (4, 6084). */
+int azg_nn_akr31_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int P, int A, int B, float* pi_dev,
+                         float* v_dev, void* stream);
 /* boards int8 [B][C][7] (reference board layout) -> x f32 [B][7][C] */
 int azg_nn_board_to_x(const int8_t* boards_dev, float* x_dev, int B, int C, void* stream);
 /* boards int8 [B][C][L] -> x f32 [B][L][ldx], columns C..ldx-1 zeroed (row stride padded to a multiple of 4 floats) */

@@ -28,7 +28,8 @@ class Args(dict):
 #  the round-based clean-up keeps ~30 plies of nodes)
 GAMES = [('minivilles', lambda: games.MinivillesGame(2), 1.0, 10), ('abalone', games.AbaloneGame, 1.0, 10), ('thelittleprince', lambda: games.TLPGame(3), 1.0, 10),
          ('botanik', games.BotanikGame, 1.0, 10), ('akropolis', games.AkropolisGame, 0.25, 10), ('smallworld', lambda: games.SmallworldGame(2), 1.0, 80),
-         ('smallworld3', lambda: games.SmallworldGame(3), 0.5, 80), ('smallworld4', lambda: games.SmallworldGame(4), 0.5, 80)]
+         ('smallworld3', lambda: games.SmallworldGame(3), 0.5, 80), ('smallworld4', lambda: games.SmallworldGame(4), 0.5, 80),
+         ('akropolis3', lambda: games.AkropolisGame(3), 0.25, 10), ('akropolis4', lambda: games.AkropolisGame(4), 0.25, 10)]
 
 
 class MlpNet(torch.nn.Module):
@@ -56,8 +57,8 @@ def main():
                     help='leaf evaluator: integer hash-net as torch ops, the same as one engine kernel (azg_eval_hashnet), MlpNet through TorchModuleEvaluator, '
                          'engine = the game\'s SHIPPED net (minivilles/pretrained_2players.pt V82, thelittleprince/pretrained_3players.pt V83: the engine\'s '
                          'MobileNet-1d kernel, nn_mb1d.hip.h; abalone/pretrained_BelgianDaisy.pt V21: nn_abalone.hip.h; smallworld/pretrained_{2,3,4}pl.pt '
-                         'V62: nn_smallworld.hip.h) as one launch; torchnet = the same weights as PyTorch-ROCm ops (nnet.MobileNet1d, nnet.AbaloneV21, '
-                         'nnet.SmallworldV62)')
+                         'V62: nn_smallworld.hip.h; akropolis/pretrained_{2,3,4}pl.pt V31: nn_akropolis.hip.h) as one launch; torchnet = the same weights as '
+                         'PyTorch-ROCm ops (nnet.MobileNet1d, nnet.AbaloneV21, nnet.SmallworldV62, nnet.AkropolisV31)')
     ap.add_argument('--md', action='store_true', help='markdown table row instead of JSON')
     ap.add_argument('--games', type=int, default=1024)
     ap.add_argument('--sims', type=int, default=200)
@@ -71,11 +72,12 @@ def main():
         g = make()
         T = max(64, int(a.games * scale))
         # (Akropolis offers hundreds of placements: with 200 simulations policy-target pruning leaves no count above 1, error bit 64)
-        args = Args(numMCTSSims=a.sims, cpuct=1.0, fpu=0.0, universes=1, forced_playouts=name != 'akropolis', prob_fullMCTS=1.0, ratio_fullMCTS=5,
+        args = Args(numMCTSSims=a.sims, cpuct=1.0, fpu=0.0, universes=1, forced_playouts=not name.startswith('akropolis'), prob_fullMCTS=1.0, ratio_fullMCTS=5,
                     dirichletAlpha=0.3, temperature=[1.25, 0.8, 1.0], tempThreshold=6)
         if a.net in ('engine', 'torchnet'):
             tag = {'minivilles': 'minivilles2_v82', 'thelittleprince': 'tlp3_v83', 'abalone': 'abalone_v21', 'smallworld': 'smallworld_v62',
-                   'smallworld3': 'smallworld3_v62', 'smallworld4': 'smallworld4_v62'}.get(name)
+                   'smallworld3': 'smallworld3_v62', 'smallworld4': 'smallworld4_v62', 'akropolis': 'akropolis_v31', 'akropolis3': 'akropolis3_v31',
+                   'akropolis4': 'akropolis4_v31'}.get(name)
             if tag is None:
                 continue
             from azg_amd import nnet
@@ -86,6 +88,9 @@ def main():
             elif name.startswith('smallworld'):     # smallworld/pretrained_{2,3,4}pl.pt V62: the one-launch transformer kernel (nn_smallworld.hip.h)
                 base = nnet.SmallworldV62.from_npz(w, num_players=g.P, device='cuda:0')
                 net = nnet.SmallworldV62Hip(base, max_batch=T) if a.net == 'engine' else base
+            elif name.startswith('akropolis'):      # akropolis/pretrained_{2,3,4}pl.pt V31: the one-launch kernel (nn_akropolis.hip.h)
+                base = nnet.AkropolisV31.from_npz(w, num_players=g.P, device='cuda:0')
+                net = nnet.AkropolisV31Hip(base, max_batch=T) if a.net == 'engine' else base
             else:
                 base = nnet.MobileNet1d.from_npz(w, device='cuda:0')
                 net = nnet.MobileNet1dHip(base, max_batch=T) if a.net == 'engine' else base

@@ -1,5 +1,5 @@
-"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets, the Abalone net and the Smallworld
-nets (HIP events, 50 forwards after warm-up)."""
+"""µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets, the Abalone net, the Smallworld
+nets and the Akropolis nets (HIP events, 50 forwards after warm-up)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -80,3 +80,29 @@ for P, tag in ((2, 'smallworld_v62'), (3, 'smallworld3_v62'), (4, 'smallworld4_v
     print('smallworld%d V62 T=%d' % (P, T), 'torch ops %.1f us' % timed(base, boards, valids.bool(), 10),
           ' k_sw62_net %.1f us' % timed(nnet.SmallworldV62Hip(base, max_batch=T), boards, valids),
           ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.SmallworldGame(P)), boards, valids, 10), flush=True)
+
+# Akropolis V31 at T for 2, 3 and 4 players: the plain-torch net (BatchNorms folded, einsum policy), the one-launch kernel, and the
+# trainable module through TorchModuleEvaluator (the reference's algorithm, its policy product summed by einsum), on random int8 boards
+# with random masks.  Floors from shapes: the reference's multiply-adds per sample (conv 5 -> 8 and 8 -> 8 per player, proj_p's
+# 1x1 (8P + 24 -> 32), depthwise and project, the 169 x 16 x 6 CS policy product) at the f32 peak (157.3 TF), and the HBM bytes
+# (boards, valid, pi, v) at 8 TB/s; the kernel's share is the larger floor over its time.
+for P, tag in ((2, 'akropolis_v31'), (3, 'akropolis3_v31'), (4, 'akropolis4_v31')):
+    CS, C = P + 2, 3 * P + 2
+    S, A = 169 * C, 1014 * CS
+    mac = P * 169 * 8 * (5 * 9 + 8 * 9) + 169 * 32 * (8 * P + 24) + 169 * 32 + 169 * 16 * 32 + CS * 6 * 169 * 16
+    t_flop = 2.0 * mac * T / 157.3e12 * 1e6
+    t_hbm = (S + A + 4 * A + 4 * P) * T / 8.0e12 * 1e6
+    base = nnet.AkropolisV31.from_npz(G + '/weights_%s.npz' % tag, num_players=P, device='cuda:0')
+    gen = torch.Generator(device='cuda:0').manual_seed(P)
+    boards = torch.randint(-128, 128, (T, S), dtype=torch.int8, device='cuda:0', generator=gen)
+    valids = (torch.rand((T, A), device='cuda:0', generator=gen) < 0.1).to(torch.uint8)
+    valids[:, 0] = 1
+    z = np.load(G + '/weights_%s.npz' % tag)
+    mod = train.AkropolisV31Module(P, A)
+    mod.load_state_dict({k[3:]: torch.as_tensor(z[k]) for k in z.files if k.startswith('sd/')}, strict=True)
+    t_k = timed(nnet.AkropolisV31Hip(base, max_batch=T), boards, valids)
+    print('akropolis%d V31 T=%d' % (P, T), 'torch ops %.1f us' % timed(base, boards, valids.bool(), 10), ' k_akr31_net %.1f us' % t_k,
+          ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.AkropolisGame(P)), boards, valids, 10),
+          ' floors: %.1f MFLOP/sample = %.1f us at the f32 peak, %.1f MB = %.1f us at 8 TB/s;  kernel at %.0f %% of the %s floor'
+          % (2e-6 * mac, t_flop, (S + 5 * A + 4 * P) * T / 1e6, t_hbm, 100 * max(t_flop, t_hbm) / t_k, 'compute' if t_flop >= t_hbm else 'HBM'),
+          flush=True)

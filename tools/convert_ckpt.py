@@ -73,19 +73,56 @@ def forward_f64(name, ckpt_rel, load_kw):
     H.cleanup()
 
 
+def forward_random(name, ckpt_rel, load_kw, n=16):
+    """netfwdrand_<name>.npz: n boards of uniformly random int8 content (codes outside the embedding's range, negative heights and
+    scores) with all-valid masks, through the reference's own module in f32 (pi, v) and in f64 (pi64, v64).  Akropolis tags only."""
+    import torch
+    m = H.load_reference(**load_kw)
+    ck = torch.load(os.path.join(H.REFERENCE, ckpt_rel), map_location='cpu', weights_only=False)
+    g = m['AkropolisGame'].AkropolisGame()
+    shape, A = tuple(g.getBoardSize()), g.getActionSize()
+    boards = np.random.default_rng(1).integers(-128, 128, size=(n,) + shape).astype(np.int8)
+    masks = np.ones((n, A), dtype=np.uint8)
+    model = ck['full_model'].eval()
+    with torch.no_grad():
+        lp, v = model(torch.from_numpy(boards.astype(np.float32)), torch.from_numpy(masks.astype(bool)))
+        lp64, v64 = model.double()(torch.from_numpy(boards.astype(np.float64)), torch.from_numpy(masks.astype(bool)))
+    out = dict(boards=boards, masks=masks, pi=torch.exp(lp).numpy(), v=v.numpy(), pi64=torch.exp(lp64).numpy(), v64=v64.numpy())
+    np.savez_compressed(os.path.join(GOLDEN, 'netfwdrand_%s.npz' % name), **out)
+    print('%-16s random boards |ref_f32 - ref_f64|: pi %.3g  v %.3g' % (name, np.abs(out['pi'] - out['pi64']).max(),
+                                                                         np.abs(out['v'] - out['v64']).max()))
+    H.cleanup()
+
+
+# tag -> (checkpoint, load_reference arguments) of every netfwd64_<tag>.npz
+F64 = [('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_players=2)),
+       ('splendor4_v80', 'splendor/pretrained_4players.pt', dict(splendor_players=4)),
+       ('santorini1_v89', 'santorini/pretrained.pt', dict(santorini_gods=1)),
+       ('azul_v84', 'azul/pretrained.pt', dict()),
+       ('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11)),
+       ('minivilles2_v82', 'minivilles/pretrained_2players.pt', dict(minivilles_players=2)),
+       ('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3)),
+       ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict()),
+       ('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2)),
+       ('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3)),
+       ('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4)),
+       ('akropolis_v31', 'akropolis/pretrained_2pl.pt', dict(akropolis_players=2)),
+       ('akropolis3_v31', 'akropolis/pretrained_3pl.pt', dict(akropolis_players=3)),
+       ('akropolis4_v31', 'akropolis/pretrained_4pl.pt', dict(akropolis_players=4))]
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == '--f64':
-        forward_f64('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_players=2))
-        forward_f64('splendor4_v80', 'splendor/pretrained_4players.pt', dict(splendor_players=4))
-        forward_f64('santorini1_v89', 'santorini/pretrained.pt', dict(santorini_gods=1))
-        forward_f64('azul_v84', 'azul/pretrained.pt', dict())
-        forward_f64('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11))
-        forward_f64('minivilles2_v82', 'minivilles/pretrained_2players.pt', dict(minivilles_players=2))
-        forward_f64('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3))
-        forward_f64('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict())
-        forward_f64('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2))
-        forward_f64('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3))
-        forward_f64('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4))
+        # `--f64` rewrites every netfwd64_*.npz; `--f64 TAG...` only those of the tags given
+        for name, ckpt_rel, load_kw in F64:
+            if len(sys.argv) == 2 or name in sys.argv[2:]:
+                forward_f64(name, ckpt_rel, load_kw)
+        return
+    if len(sys.argv) > 2 and sys.argv[1] == '--random':
+        # `--random TAG...`: netfwdrand_<tag>.npz, random int8 boards with all-valid masks through the reference module (f32 and f64)
+        for name, ckpt_rel, load_kw in F64:
+            if name in sys.argv[2:]:
+                forward_random(name, ckpt_rel, load_kw)
         return
     if len(sys.argv) > 2 and sys.argv[1] == '--only':
         return convert(*{'santorini11_v78': ('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11),
@@ -105,7 +142,16 @@ def main():
                          'smallworld3_v62': ('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3), 'SmallworldGame',
                                              'SmallworldGame', 128),
                          'smallworld4_v62': ('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4), 'SmallworldGame',
-                                             'SmallworldGame', 128)}[sys.argv[2]])
+                                             'SmallworldGame', 128),
+                         # AkropolisNNet.py nn_version 31 (all three shipped checkpoints): board convolutions per player, a kernel-1
+                         # InvertedResidual over the cells and a bilinear policy per construction-site tile; engine net through
+                         # nn_akropolis.hip.h
+                         'akropolis_v31': ('akropolis_v31', 'akropolis/pretrained_2pl.pt', dict(akropolis_players=2), 'AkropolisGame',
+                                           'AkropolisGame', 128),
+                         'akropolis3_v31': ('akropolis3_v31', 'akropolis/pretrained_3pl.pt', dict(akropolis_players=3), 'AkropolisGame',
+                                            'AkropolisGame', 128),
+                         'akropolis4_v31': ('akropolis4_v31', 'akropolis/pretrained_4pl.pt', dict(akropolis_players=4), 'AkropolisGame',
+                                            'AkropolisGame', 128)}[sys.argv[2]])
     convert('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_players=2), 'SplendorGame', 'SplendorGame')
     convert('splendor4_v80', 'splendor/pretrained_4players.pt', dict(splendor_players=4), 'SplendorGame', 'SplendorGame', n_vec=128)
     convert('santorini1_v89', 'santorini/pretrained.pt', dict(santorini_gods=1), 'SantoriniGame', 'SantoriniGame', n_vec=128)
