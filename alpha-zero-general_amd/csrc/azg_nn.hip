@@ -265,7 +265,7 @@ extern "C" int azg_nn_debug_phase_times_h2(long long* out /* [4][16] */) {
 #endif
 
 // ---- whole MobileNet-1d forward, any supported geometry, one launch (nn_mb1d.hip.h) ----
-// (the geometries CfgSplendor2 / 3 / 4, CfgAzul, CfgMinivilles2, CfgTLP3: nn_mb1d.hip.h)
+// (the geometries CfgSplendor2 / 3 / 4, CfgAzul, CfgMinivilles2 / 3 / 4, CfgTLP3 / 4 / 5: nn_mb1d.hip.h)
 
 template <class CF, bool H2>
 static int launch_mb1d(const Mb1dNetW& N, const int8_t* boards, const uint8_t* valid, int B, float* pi, float* v, hipStream_t s) {
@@ -302,6 +302,10 @@ static int mb1d_forward(int geometry, const int8_t* boards, const uint8_t* valid
         case AZG_NET_AZUL: return launch_mb1d<CfgAzul, H2>(N, boards, valid, B, pi, v, s);
         case AZG_NET_MINIVILLES2: return launch_mb1d<CfgMinivilles2, H2>(N, boards, valid, B, pi, v, s);
         case AZG_NET_TLP3: return launch_mb1d<CfgTLP3, H2>(N, boards, valid, B, pi, v, s);
+        case AZG_NET_MINIVILLES3: return launch_mb1d<CfgMinivilles3, H2>(N, boards, valid, B, pi, v, s);
+        case AZG_NET_MINIVILLES4: return launch_mb1d<CfgMinivilles4, H2>(N, boards, valid, B, pi, v, s);
+        case AZG_NET_TLP4: return launch_mb1d<CfgTLP4, H2>(N, boards, valid, B, pi, v, s);
+        case AZG_NET_TLP5: return launch_mb1d<CfgTLP5, H2>(N, boards, valid, B, pi, v, s);
         default: return fail("azg_nn_mb1d_forward: unknown geometry");
     }
 }

@@ -45,7 +45,10 @@ struct Mb1dCfg {
     static constexpr int AP = mb_r16(A), AS = AP + 4;
     // LDS map (floats)
     static constexpr int XA_SZ = ROWSP * (XS > OS ? XS : OS), X2_SZ = ROWSP * XS, H_SZ = ROWSP * HS;
-    static constexpr int PL_SZ = NS * HS, SC_SZ = (ROWSP / L + 1) * HS, SH_SZ = 16 * QS;
+    // SC: one SE scale row per sample; the project GEMM's padding rows (< ROWSP) read up to row ROWSP / L.  PL: the pooled rows -- at
+    // least NS, and enough that the 16 rows the SE fc1 GEMM reads (rows >= NS are scratch) stay inside PL + SC (NS < 8 at 15 tokens)
+    static constexpr int SC_ROWS = ROWSP / L + 1, PL_ROWS = NS > 16 - SC_ROWS ? NS : 16 - SC_ROWS;
+    static constexpr int PL_SZ = PL_ROWS * HS, SC_SZ = SC_ROWS * HS, SH_SZ = 16 * QS;
     static constexpr int KS_PI = AP / 16 >= NW ? 1 : NW / (AP / 16);    // K slices of the policy head GEMMs
     static constexpr int HEAD_PI = (KS_PI + 1) * 16 * AS, HEAD_V = NW * 16 * 20;     // RED[KS][16][AS] + HID; value RED[NW][16][20]
     static constexpr int HEAD_SZ = HEAD_PI > HEAD_V ? HEAD_PI : HEAD_V;              // aliases H
@@ -55,6 +58,12 @@ struct Mb1dCfg {
     static constexpr bool WD_REGS = L_ * L_ <= 64;
     static constexpr int WD_LD = WD_REGS ? L_ : (L_ + 3) / 4 * 4, WD_SZ = WD_REGS ? 64 : L_ * WD_LD;
     static constexpr int LDS_FLOATS = XA_SZ + X2_SZ + H_ALLOC + PL_SZ + SC_SZ + SH_SZ + WD_SZ;
+    // what the body (mb1d_net_body, mb_block, mb_head_gemm*) takes for granted
+    static_assert(NS >= 1 && NS <= 16, "the SE GEMMs and the Flatten -> Linear heads hold the workgroup's samples in ONE 16-row tile");
+    static_assert(PL_ROWS + SC_ROWS >= 16, "the SE fc1 GEMM reads 16 pooled rows");
+    static_assert(XS <= HS, "the int8 board tile X0 [ROWSP][XS] is staged in H");
+    static_assert(P_ <= 16 && NS * P_ <= NW * 64, "the value head is one 16-column tile (RED row stride 20) and one thread per (sample, player)");
+    static_assert(E0 >= C_ && E1 >= C_ && E2 >= C_, "the expanded width is at least the channel count (row strides)");
 };
 
 // One GEMM phase over the workgroup:  out(row, 16*ct + 4g .. +3) = epi( sum_k in[row][k] * W[k][col] )
@@ -544,5 +553,14 @@ typedef Mb1dCfg<6, 23, 16, 180, 2, 115, 115, 46, 32, 32, 16, 46, 1, 2, 0> CfgAzu
 // TLPNNet.py:175-196 nn_version 83, 3 players: [55][15] board)
 typedef Mb1dCfg<2, 58, 16, 21, 2, 174, 174, 174, 40, 40, 40, 58, 1, 2, 1> CfgMinivilles2;
 typedef Mb1dCfg<15, 55, 8, 9, 3, 82, 82, 82, 24, 24, 24, 55, 1, 2, 1> CfgTLP3;
+// the other player counts of both games (MinivillesNNet.py:101-123 with C = 18 + 20 P, E = 3C: [78][2] / [98][2] boards, 3 / 4 players;
+// TLPNNet.py:175-196 with C = 1 + 18 P, E = int(1.5 C): [73][15] / [91][15] boards, 4 / 5 players).  NS, timed on the GPU against one
+// alternative each: Minivilles keeps the 16 samples of CfgMinivilles2 (94 / 119 KB of LDS; NS = 8 is 1.5x slower).  The TLP
+// nets do not fit at NS = 8 (170 / 205 KB) and run one 768-thread workgroup per CU at any NS that fits (> 80 KB): both take NS = 6 (90 of
+// 96 rows, 127 / 153 KB); NS = 4 was 5 % / 7 % slower on the default f16 x 2 path.
+typedef Mb1dCfg<2, 78, 16, 21, 3, 234, 234, 234, 56, 56, 56, 78, 1, 2, 1> CfgMinivilles3;
+typedef Mb1dCfg<2, 98, 16, 21, 4, 294, 294, 294, 72, 72, 72, 98, 1, 2, 1> CfgMinivilles4;
+typedef Mb1dCfg<15, 73, 6, 16, 4, 109, 109, 109, 32, 32, 32, 73, 1, 2, 1> CfgTLP4;
+typedef Mb1dCfg<15, 91, 6, 25, 5, 136, 136, 136, 32, 32, 32, 91, 1, 2, 1> CfgTLP5;
 
 }  // namespace azg

@@ -63,3 +63,51 @@ def load_reference_checkpoint(path):
     sd = {k: v.numpy() for k, v in ck['state_dict'].items()}
     args = {k: v for k, v in ck.items() if k not in ('state_dict', 'full_model')}
     return sd, args
+
+
+# ---- stand-in weights for a shipped checkpoint too large to keep as a test fixture ----
+# A net's f32 weights barely compress (Minivilles 4p: 1.3 MB raw, 1.2 MB deflated).  For such a checkpoint the fixture keeps the
+# shapes and per-tensor statistics of its state_dict (`weightstats_<tag>.npz`, tools/convert_ckpt.py) and the weights are drawn from
+# them with numpy's PCG64 generator, which gives the same numbers on every platform; the reference's own module is evaluated on those
+# weights for the forward vectors.
+def weight_stats(state_dict, seed=0):
+    """state_dict (numpy arrays) -> the arrays of a weightstats_<tag>.npz: 'shape/<key>', 'stat/<key>' = (mean, std) -- of log(x)
+    for BatchNorm running variances, which must stay positive --, integer tensors ('int/<key>') kept as they are, and the seed"""
+    out = {'seed': np.array(seed)}
+    for k, v in state_dict.items():
+        v = np.asarray(v)
+        if not np.issubdtype(v.dtype, np.floating):
+            out['int/' + k] = v
+            continue
+        x = np.log(v.astype(np.float64)) if k.endswith('running_var') else v.astype(np.float64)
+        out['shape/' + k] = np.array(v.shape, dtype=np.int64)
+        out['stat/' + k] = np.array([x.mean(), x.std()])
+    return out
+
+
+def synthetic_state_dict(z):
+    """the stand-in state_dict (float32 numpy arrays) of a weightstats_<tag>.npz: keys in sorted order, each tensor drawn as
+    mean + std * N(0, 1) (exp of that for running variances) from one PCG64 stream"""
+    files = list(z.files) if hasattr(z, 'files') else list(z)
+    rng = np.random.default_rng(int(z['seed']))
+    sd = {}
+    for name in sorted(n[6:] for n in files if n.startswith('shape/')):
+        mean, std = (float(t) for t in z['stat/' + name])
+        x = mean + std * rng.standard_normal(tuple(int(s) for s in z['shape/' + name]))
+        sd[name] = (np.exp(x) if name.endswith('running_var') else x).astype(np.float32)
+    sd.update({n[4:]: np.asarray(z[n]) for n in files if n.startswith('int/')})
+    return sd
+
+
+def fixture_state_dict(golden_dir, tag):
+    """(state_dict as numpy arrays, {arg: value}) of a net fixture: the shipped weights of weights_<tag>.npz, or the stand-in weights of
+    weightstats_<tag>.npz for a checkpoint too large to keep"""
+    import os
+    path = os.path.join(golden_dir, 'weights_%s.npz' % tag)
+    if os.path.exists(path):
+        z = np.load(path)
+        sd = {k[3:]: np.asarray(z[k]) for k in z.files if k.startswith('sd/')}
+    else:
+        z = np.load(os.path.join(golden_dir, 'weightstats_%s.npz' % tag))
+        sd = synthetic_state_dict(z)
+    return sd, {k[4:]: z[k] for k in z.files if k.startswith('arg/')}

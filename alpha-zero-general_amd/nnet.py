@@ -456,9 +456,11 @@ class AzulV84(SplendorV80):
 class MobileNet1d(AzulV84):
     """Any net of the reference's one-trunk-block MobileNetV3-1d family, geometry read off the state_dict: first_layer, ONE trunk block
     (ReLU, mean squeeze), one policy-head and one value-head block (Hardswish, `head_se` squeeze), Flatten + Linear + ReLU + Linear heads.
-    The shipped nets of two more games are of this shape (their checkpoints load unchanged):
-      minivilles/MinivillesNNet.py:101-123 nn_version 82 -- [B, 58, 2] board (2 players), blocks 58 -> 174 -> 58, heads Linear(116, 21) / (116, 2)
-      thelittleprince/TLPNNet.py:175-196 nn_version 83   -- [B, 55, 15] board (3 players), blocks 55 -> 82 -> 55, heads Linear(825, 9) / (825, 3)
+    The shipped nets of two more games are of this shape at every shipped player count (their checkpoints load unchanged):
+      minivilles/MinivillesNNet.py:101-123 nn_version 82 -- [B, 58, 2] board (2 players), blocks 58 -> 174 -> 58, heads Linear(116, 21) / (116, 2);
+                                                           C = 18 + 20 P and E = 3C for 3 / 4 players ([B, 78 | 98, 2])
+      thelittleprince/TLPNNet.py:175-196 nn_version 83   -- [B, 55, 15] board (3 players), blocks 55 -> 82 -> 55, heads Linear(825, 9) / (825, 3);
+                                                           C = 1 + 18 P and E = int(1.5 C) for 4 / 5 players ([B, 73 | 91, 15])
     (TLP nn_version 80 / 82 differ in the expansion factor only and load the same way.)"""
 
     def __init__(self, state_dict, num_players=None, head_se='max', device='cuda:0', dtype=torch.float32):
@@ -485,11 +487,18 @@ class MobileNet1d(AzulV84):
 
 
 class MinivillesV82(MobileNet1d):
-    """minivilles/MinivillesNNet.py nn_version == 82 (:101-123,166-172), the net of minivilles/pretrained_2players.pt"""
+    """minivilles/MinivillesNNet.py nn_version == 82 (:101-123,166-172), the net of all shipped player counts
+    (minivilles/pretrained_{2,3,4}players.pt: [58 | 78 | 98][2] boards)"""
 
 
 class TLPV83(MobileNet1d):
-    """thelittleprince/TLPNNet.py nn_version == 83 (:175-196,211-217), the net of thelittleprince/pretrained_3players.pt"""
+    """thelittleprince/TLPNNet.py nn_version == 83 (:175-196,211-217), the net of all shipped player counts
+    (thelittleprince/pretrained_{3,4,5}players.pt: [55 | 73 | 91][15] boards)"""
+
+
+# (tokens L, channels C) -> AZG_NET_* geometry id of azg_nn_mb1d_forward (include/azg.h)
+MB1D_GEOMETRY = {(7, 56): 0, (7, 71): 1, (7, 88): 2, (6, 23): 3, (2, 58): 4, (15, 55): 5,
+                 (2, 78): 6, (2, 98): 7, (15, 73): 8, (15, 91): 9}
 
 
 class MobileNet1dHip:
@@ -552,7 +561,7 @@ class MobileNet1dHip:
         self.pWv1 = flat(base.Wv1, gv['cout'], gv['coutp'])
         self.bpi1, self.bpi2, self.bv1 = base.bpi1.contiguous(), base.bpi2.contiguous(), base.bv1.contiguous()
         self.Wv2, self.bv2 = base.Wv2.contiguous(), base.bv2.contiguous()
-        self.geometry = {(7, 56): 0, (7, 71): 1, (7, 88): 2, (6, 23): 3, (2, 58): 4, (15, 55): 5}.get((self.L, self.C))    # AZG_NET_* of azg.h
+        self.geometry = MB1D_GEOMETRY.get((self.L, self.C))
         self.fused = fused and self.geometry is not None
         if not self.fused and self.geometry not in (0, 1, 2, 3):
             # the launch-per-layer path (azg_nn_linear's tile shapes) exists for the Splendor and Azul geometries only

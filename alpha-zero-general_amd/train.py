@@ -63,30 +63,59 @@ class _Block(nn.Module):
         return y + x if self.use_res_connect else y
 
 
-class SplendorV80Module(nn.Module):
-    version = 80
+class _MobileNet1dModule(nn.Module):
+    """The reference's one-trunk-block MobileNetV3-1d nets with its parameter names: [B, C, L] boards (no transpose), first_layer, ONE
+    trunk block C -> E -> C (ReLU, mean squeeze), policy / value head blocks C -> E -> C (Hardswish, max squeeze) + Flatten + Linear +
+    ReLU + Linear, dropout after the trunk in training mode (splendor/SplendorNNet.py:397-440, MinivillesNNet.py:101-123,166-172,
+    TLPNNet.py:175-217)"""
 
-    def __init__(self, num_players=2, action_size=81, dropout=0.0):
+    def __init__(self, C, L, E, num_players, action_size, dropout):
         super().__init__()
-        self.C = 32 + 10 * num_players + num_players * num_players
-        self.P, self.A, self.dropout = num_players, action_size, dropout
-        C = self.C
+        self.C, self.L, self.P, self.A, self.dropout = C, L, num_players, action_size, dropout
         self.first_layer = _LinearNormAct(C, C, None)
-        self.trunk = nn.Sequential(_Block(C, 3 * C, False, 'avg'))
-        self.output_layers_PI = nn.Sequential(_Block(C, 3 * C, True, 'max'), nn.Flatten(1), nn.Linear(7 * C, action_size), nn.ReLU(),
+        self.trunk = nn.Sequential(_Block(C, E, False, 'avg', tokens=L))
+        self.output_layers_PI = nn.Sequential(_Block(C, E, True, 'max', tokens=L), nn.Flatten(1), nn.Linear(L * C, action_size), nn.ReLU(),
                                               nn.Linear(action_size, action_size))
-        self.output_layers_V = nn.Sequential(_Block(C, 3 * C, True, 'max'), nn.Flatten(1), nn.Linear(7 * C, num_players), nn.ReLU(),
+        self.output_layers_V = nn.Sequential(_Block(C, E, True, 'max', tokens=L), nn.Flatten(1), nn.Linear(L * C, num_players), nn.ReLU(),
                                              nn.Linear(num_players, num_players))
         self.register_buffer('lowvalue', torch.FloatTensor([-1e8]))
 
     def forward(self, boards, valid_actions):
         """-> (log pi [B, A], v [B, P]) like the reference module"""
-        x = boards.reshape(-1, self.C, 7).float()
+        x = boards.reshape(-1, self.C, self.L).float()
         x = self.first_layer(x)
         x = F.dropout(self.trunk(x), p=self.dropout, training=self.training)
         v = self.output_layers_V(x)
         pi = torch.where(valid_actions.bool(), self.output_layers_PI(x), self.lowvalue)
         return F.log_softmax(pi, dim=1), torch.tanh(v)
+
+
+class SplendorV80Module(_MobileNet1dModule):
+    version = 80
+
+    def __init__(self, num_players=2, action_size=81, dropout=0.0):
+        C = 32 + 10 * num_players + num_players * num_players
+        super().__init__(C, 7, 3 * C, num_players, action_size, dropout)
+
+
+class MinivillesV82Module(_MobileNet1dModule):
+    """minivilles/MinivillesNNet.py nn_version 82 (:101-123,166-172): [B, C, 2] boards with C = 18 + 20 P (58 / 78 / 98 for the
+    shipped 2 / 3 / 4-player checkpoints), blocks C -> 3C -> C"""
+    version = 82
+
+    def __init__(self, num_players=2, action_size=21, dropout=0.0):
+        C = 18 + 20 * num_players
+        super().__init__(C, 2, 3 * C, num_players, action_size, dropout)
+
+
+class TLPV83Module(_MobileNet1dModule):
+    """thelittleprince/TLPNNet.py nn_version 83 (:175-217): [B, C, 15] boards with C = 1 + 18 P (55 / 73 / 91 for the shipped
+    3 / 4 / 5-player checkpoints), blocks C -> int(1.5 C) -> C"""
+    version = 83
+
+    def __init__(self, num_players=3, action_size=9, dropout=0.0):
+        C = 1 + 18 * num_players
+        super().__init__(C, 15, int(1.5 * C), num_players, action_size, dropout)
 
 
 class AzulV84Module(nn.Module):

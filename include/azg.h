@@ -371,8 +371,9 @@ int azg_nn_v80_forward_h2(const int8_t* boards_dev, const uint8_t* valid_dev, co
                           int B, int P, float* pi_dev, float* v_dev, void* stream);
 /* The whole MobileNetV3-1d forward (first layer, trunk block, policy block + head, value block + head) in one launch for
    the geometries of the reference's Splendor (SplendorNNet.py:259-283, n players: C = 32 + 10n + n^2 channels x 7 tokens)
-   and Azul (AzulNNet.py:91-113: 23 channels x 6 tokens) nets, and of the shipped nets of Minivilles (MinivillesNNet.py:101-123: 58 x 2)
-   and The Little Prince (TLPNNet.py:175-196: 55 x 15) -- the generic sibling of azg_nn_v80_forward.
+   and Azul (AzulNNet.py:91-113: 23 channels x 6 tokens) nets, and of the shipped nets of Minivilles (MinivillesNNet.py:101-123,
+   n players: C = 18 + 20n channels x 2 tokens) and The Little Prince (TLPNNet.py:175-196, n players: C = 1 + 18n channels x 15 tokens),
+   every shipped player count -- the generic sibling of azg_nn_v80_forward.  An unknown geometry id returns an error and launches nothing.
    boards int8 [B][C][L], valid u8 [B][A] -> pi f32 [B][A] (probabilities), v f32 [B][P].  w = 43 device pointers:
    {W0, b0}, 3 x {We, be, Wd[L][L], bn_scale_d, bn_bias_d, W1, b1, W2, b2, Wp, bp} (trunk, policy head, value head),
    {Wpi1, bpi1, Wpi2, bpi2, Wv1, bv1, Wv2[P][P], bv2}; every matrix but Wd / Wv2 is zero-padded to multiples of 16 in both
@@ -381,7 +382,11 @@ int azg_nn_v80_forward_h2(const int8_t* boards_dev, const uint8_t* valid_dev, co
    policy-block channels)/16) + 4. */
 enum { AZG_NET_SPLENDOR2 = 0, AZG_NET_SPLENDOR3 = 1, AZG_NET_SPLENDOR4 = 2, AZG_NET_AZUL = 3,
        AZG_NET_MINIVILLES2 = 4,   /* minivilles/MinivillesNNet.py:101-123 nn_version 82, 2 players: C = 58, L = 2, A = 21 */
-       AZG_NET_TLP3 = 5 };        /* thelittleprince/TLPNNet.py:175-196 nn_version 83, 3 players: C = 55, L = 15, A = 9 */
+       AZG_NET_TLP3 = 5,          /* thelittleprince/TLPNNet.py:175-196 nn_version 83, 3 players: C = 55, L = 15, A = 9 */
+       AZG_NET_MINIVILLES3 = 6,   /* minivilles/MinivillesNNet.py:101-123 nn_version 82, 3 players: C = 78, L = 2, A = 21 */
+       AZG_NET_MINIVILLES4 = 7,   /* minivilles/MinivillesNNet.py:101-123 nn_version 82, 4 players: C = 98, L = 2, A = 21 */
+       AZG_NET_TLP4 = 8,          /* thelittleprince/TLPNNet.py:175-196 nn_version 83, 4 players: C = 73, L = 15, A = 16 */
+       AZG_NET_TLP5 = 9 };        /* thelittleprince/TLPNNet.py:175-196 nn_version 83, 5 players: C = 91, L = 15, A = 25 */
 int azg_nn_mb1d_forward(int geometry, const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int B,
                         float* pi_dev, float* v_dev, void* stream);
 /* The same forward with every GEMM phase on f16 x 2 split-precision operands (hi + lo halves, three v_mfma_f32_16x16x32_f16 per

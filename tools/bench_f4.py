@@ -29,7 +29,9 @@ class Args(dict):
 GAMES = [('minivilles', lambda: games.MinivillesGame(2), 1.0, 10), ('abalone', games.AbaloneGame, 1.0, 10), ('thelittleprince', lambda: games.TLPGame(3), 1.0, 10),
          ('botanik', games.BotanikGame, 1.0, 10), ('akropolis', games.AkropolisGame, 0.25, 10), ('smallworld', lambda: games.SmallworldGame(2), 1.0, 80),
          ('smallworld3', lambda: games.SmallworldGame(3), 0.5, 80), ('smallworld4', lambda: games.SmallworldGame(4), 0.5, 80),
-         ('akropolis3', lambda: games.AkropolisGame(3), 0.25, 10), ('akropolis4', lambda: games.AkropolisGame(4), 0.25, 10)]
+         ('akropolis3', lambda: games.AkropolisGame(3), 0.25, 10), ('akropolis4', lambda: games.AkropolisGame(4), 0.25, 10),
+         ('minivilles3', lambda: games.MinivillesGame(3), 1.0, 10), ('minivilles4', lambda: games.MinivillesGame(4), 1.0, 10),
+         ('tlp4', lambda: games.TLPGame(4), 1.0, 10), ('tlp5', lambda: games.TLPGame(5), 1.0, 10)]
 
 
 class MlpNet(torch.nn.Module):
@@ -55,7 +57,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--net', default='hash', choices=['hash', 'hashhip', 'mlp', 'engine', 'torchnet'],
                     help='leaf evaluator: integer hash-net as torch ops, the same as one engine kernel (azg_eval_hashnet), MlpNet through TorchModuleEvaluator, '
-                         'engine = the game\'s SHIPPED net (minivilles/pretrained_2players.pt V82, thelittleprince/pretrained_3players.pt V83: the engine\'s '
+                         'engine = the game\'s SHIPPED net (minivilles/pretrained_{2,3,4}players.pt V82, thelittleprince/pretrained_{3,4,5}players.pt V83: the engine\'s '
                          'MobileNet-1d kernel, nn_mb1d.hip.h; abalone/pretrained_BelgianDaisy.pt V21: nn_abalone.hip.h; smallworld/pretrained_{2,3,4}pl.pt '
                          'V62: nn_smallworld.hip.h; akropolis/pretrained_{2,3,4}pl.pt V31: nn_akropolis.hip.h) as one launch; torchnet = the same weights as '
                          'PyTorch-ROCm ops (nnet.MobileNet1d, nnet.AbaloneV21, nnet.SmallworldV62, nnet.AkropolisV31)')
@@ -77,7 +79,8 @@ def main():
         if a.net in ('engine', 'torchnet'):
             tag = {'minivilles': 'minivilles2_v82', 'thelittleprince': 'tlp3_v83', 'abalone': 'abalone_v21', 'smallworld': 'smallworld_v62',
                    'smallworld3': 'smallworld3_v62', 'smallworld4': 'smallworld4_v62', 'akropolis': 'akropolis_v31', 'akropolis3': 'akropolis3_v31',
-                   'akropolis4': 'akropolis4_v31'}.get(name)
+                   'akropolis4': 'akropolis4_v31', 'minivilles3': 'minivilles3_v82', 'minivilles4': 'minivilles4_v82', 'tlp4': 'tlp4_v83',
+                   'tlp5': 'tlp5_v83'}.get(name)
             if tag is None:
                 continue
             from azg_amd import nnet
@@ -91,8 +94,9 @@ def main():
             elif name.startswith('akropolis'):      # akropolis/pretrained_{2,3,4}pl.pt V31: the one-launch kernel (nn_akropolis.hip.h)
                 base = nnet.AkropolisV31.from_npz(w, num_players=g.P, device='cuda:0')
                 net = nnet.AkropolisV31Hip(base, max_batch=T) if a.net == 'engine' else base
-            else:
-                base = nnet.MobileNet1d.from_npz(w, device='cuda:0')
+            else:                           # (Minivilles 4p: the stand-in weights of the same shapes, weightstats_minivilles4_v82.npz)
+                from azg_amd import formats
+                base = nnet.MobileNet1d(formats.fixture_state_dict(os.path.join(ROOT, 'tests', 'golden'), tag)[0], device='cuda:0')
                 net = nnet.MobileNet1dHip(base, max_batch=T) if a.net == 'engine' else base
         elif a.net == 'mlp':
             from azg_amd.nnet import TorchModuleEvaluator

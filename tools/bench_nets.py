@@ -1,5 +1,5 @@
 """µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets, the Abalone net, the Smallworld
-nets and the Akropolis nets (HIP events, 50 forwards after warm-up)."""
+nets and the Akropolis nets (HIP events, 50 forwards after warm-up), and the shipped MobileNet-1d checkpoints of every player count."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -106,3 +106,30 @@ for P, tag in ((2, 'akropolis_v31'), (3, 'akropolis3_v31'), (4, 'akropolis4_v31'
           ' floors: %.1f MFLOP/sample = %.1f us at the f32 peak, %.1f MB = %.1f us at 8 TB/s;  kernel at %.0f %% of the %s floor'
           % (2e-6 * mac, t_flop, (S + 5 * A + 4 * P) * T / 1e6, t_hbm, 100 * max(t_flop, t_hbm) / t_k, 'compute' if t_flop >= t_hbm else 'HBM'),
           flush=True)
+
+# The shipped MobileNet-1d checkpoints the one-launch kernel runs at their own geometries (Splendor 3p, Minivilles 3 / 4p, The Little Prince
+# 4 / 5p): the plain-torch net, k_mb1d_net f32 and h2, on the fixture boards tiled to T.  Floors from shapes: multiply-adds per sample (first
+# layer L C^2; per block expand and project 2 L C E, token mix L^2 E, SE 2 E Q; heads L C (A + P) + A^2 + P^2) at the f32 peak (157.3 TF),
+# and the HBM bytes (f32 weights once, int8 boards, u8 valid, f32 pi and v) at 8 TB/s; the kernel's share is the larger floor over its time.
+for tag in ('splendor3_v80', 'minivilles3_v82', 'minivilles4_v82', 'tlp4_v83', 'tlp5_v83'):
+    from azg_amd import formats   # (Minivilles 4p: the stand-in weights of the same shapes, weightstats_minivilles4_v82.npz)
+    sd = formats.fixture_state_dict(G, tag)[0]
+    base = nnet.MobileNet1d(sd, device='cuda:0')
+    L, C, A, P = base.L, base.nb_vect, base.A, base.P
+    blocks = (base.trunk, base.head_pi, base.head_v)
+    mac = L * C * C + sum(2 * L * C * b.We.shape[1] + L * L * b.We.shape[1] + 2 * b.We.shape[1] * b.W1.shape[1] for b in blocks) \
+        + L * C * (A + P) + A * A + P * P
+    n_w = sum(int(np.prod(v.shape)) for v in sd.values())
+    t_flop = 2.0 * mac * T / 157.3e12 * 1e6
+    hbm = 4 * n_w + (C * L + A + 4 * A + 4 * P) * T
+    t_hbm = hbm / 8.0e12 * 1e6
+    d = np.load(G + '/netfwd_%s.npz' % tag)
+    idx = np.arange(T) % len(d['boards'])
+    boards = torch.from_numpy(d['boards'][idx].reshape(T, -1)).to('cuda:0')
+    valids = torch.from_numpy(d['masks'][idx]).to('cuda:0')
+    t32 = timed(nnet.MobileNet1dHip(base, max_batch=T, h2=False), boards, valids)
+    th2 = timed(nnet.MobileNet1dHip(base, max_batch=T, h2=True), boards, valids)
+    print('%s T=%d' % (tag, T), 'torch ops %.1f us' % timed(base, boards, valids.bool(), 10), ' k_mb1d_net f32 %.1f us' % t32,
+          ' k_mb1d_net h2 %.1f us' % th2,
+          ' floors: %.2f MFLOP/sample = %.1f us at the f32 peak, %.1f MB = %.1f us at 8 TB/s;  h2 kernel at %.0f %% of the %s floor'
+          % (2e-6 * mac, t_flop, hbm / 1e6, t_hbm, 100 * max(t_flop, t_hbm) / th2, 'compute' if t_flop >= t_hbm else 'HBM'), flush=True)

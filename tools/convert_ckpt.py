@@ -13,6 +13,20 @@ sys.path.insert(0, os.path.join(HERE, 'refshim'))
 import harness as H  # noqa: E402
 
 GOLDEN = os.path.join(HERE, '..', 'tests', 'golden')
+# checkpoints whose weights are too large to keep as a fixture (Minivilles 4p: 1.3 MB of f32 that does not compress): the fixture is
+# weightstats_<tag>.npz (shapes and per-tensor statistics, azg_amd.formats.weight_stats) and the forward vectors are the reference
+# module's outputs on the stand-in weights drawn from it (formats.synthetic_state_dict)
+STANDIN = {'minivilles4_v82': 4}
+
+
+def _standin(name, model):
+    """load the stand-in weights of weightstats_<name>.npz into the reference's module (strict: every key, every shape)"""
+    import torch
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    from azg_amd import formats
+    sd = formats.synthetic_state_dict(np.load(os.path.join(GOLDEN, 'weightstats_%s.npz' % name)))
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return model
 
 
 def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True):
@@ -21,13 +35,18 @@ def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True
     ck = torch.load(os.path.join(H.REFERENCE, ckpt_rel), map_location='cpu', weights_only=False)
     sd = {k: v.numpy() for k, v in ck['state_dict'].items()}
     meta = {k: ck[k] for k in ck if k not in ('state_dict', 'full_model')}
-    out = {'sd/' + k: v for k, v in sd.items()}
+    if name in STANDIN:
+        sys.path.insert(0, os.path.join(HERE, '..'))
+        from azg_amd import formats
+        out = formats.weight_stats(sd, seed=STANDIN[name])
+    else:
+        out = {'sd/' + k: v for k, v in sd.items()}
     for k, v in meta.items():
         if isinstance(v, (int, float, bool)):
             out['arg/' + k] = np.array(v)
         elif isinstance(v, (list, tuple)) and all(isinstance(x, (int, float)) for x in v):
             out['arg/' + k] = np.array(v, dtype=np.float64)
-    np.savez_compressed(os.path.join(GOLDEN, 'weights_%s.npz' % name), **out)
+    np.savez_compressed(os.path.join(GOLDEN, '%s_%s.npz' % ('weightstats' if name in STANDIN else 'weights', name)), **out)
     print(name, 'args:', {k: v for k, v in meta.items() if k in ('nn_version', 'cpuct', 'fpu', 'universes', 'numMCTSSims',
                                                                    'dirichletAlpha', 'temperature', 'tempThreshold')})
     if not forward:      # the pickled full_model needs the real torchvision (absent here): weights + args only
@@ -36,6 +55,8 @@ def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True
         return
     # G4: forward vectors from the reference's own module (GenericNNetWrapper.py:112-120 torch branch)
     model = ck['full_model'].eval()
+    if name in STANDIN:
+        model = _standin(name, model)
     env = np.load(os.path.join(GOLDEN, 'env_%s.npz' % name.split('_')[0]))
     rng = np.random.default_rng(0)
     sel = rng.choice(len(env['canonical']), size=min(n_vec, len(env['canonical'])), replace=False)
@@ -58,7 +79,10 @@ def forward_f64(name, ckpt_rel, load_kw):
     import torch
     H.load_reference(**load_kw)
     ck = torch.load(os.path.join(H.REFERENCE, ckpt_rel), map_location='cpu', weights_only=False)
-    model = ck['full_model'].eval().double()
+    model = ck['full_model'].eval()
+    if name in STANDIN:
+        model = _standin(name, model)
+    model = model.double()
     if hasattr(model, 'stem'):
         # SmallworldNNet.py InputStem.forward hard-codes .float() on the num_proj / bit_proj inputs: recast them to f64 on the way
         # in (forward pre-hooks; the reference's source stays as it is)
@@ -102,6 +126,11 @@ F64 = [('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_player
        ('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11)),
        ('minivilles2_v82', 'minivilles/pretrained_2players.pt', dict(minivilles_players=2)),
        ('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3)),
+       ('splendor3_v80', 'splendor/pretrained_3players.pt', dict(splendor_players=3)),
+       ('minivilles3_v82', 'minivilles/pretrained_3players.pt', dict(minivilles_players=3)),
+       ('minivilles4_v82', 'minivilles/pretrained_4players.pt', dict(minivilles_players=4)),
+       ('tlp4_v83', 'thelittleprince/pretrained_4players.pt', dict(tlp_players=4)),
+       ('tlp5_v83', 'thelittleprince/pretrained_5players.pt', dict(tlp_players=5)),
        ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict()),
        ('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2)),
        ('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3)),
@@ -132,6 +161,15 @@ def main():
                          'minivilles2_v82': ('minivilles2_v82', 'minivilles/pretrained_2players.pt', dict(minivilles_players=2),
                                              'MinivillesGame', 'MinivillesGame', 128),
                          'tlp3_v83': ('tlp3_v83', 'thelittleprince/pretrained_3players.pt', dict(tlp_players=3), 'TLPGame', 'TLPGame', 128),
+                         # the other shipped checkpoints of the family (every player count): the same kernel at their own geometries
+                         'splendor3_v80': ('splendor3_v80', 'splendor/pretrained_3players.pt', dict(splendor_players=3), 'SplendorGame',
+                                           'SplendorGame', 128),
+                         'minivilles3_v82': ('minivilles3_v82', 'minivilles/pretrained_3players.pt', dict(minivilles_players=3),
+                                             'MinivillesGame', 'MinivillesGame', 128),
+                         'minivilles4_v82': ('minivilles4_v82', 'minivilles/pretrained_4players.pt', dict(minivilles_players=4),
+                                             'MinivillesGame', 'MinivillesGame', 128),
+                         'tlp4_v83': ('tlp4_v83', 'thelittleprince/pretrained_4players.pt', dict(tlp_players=4), 'TLPGame', 'TLPGame', 128),
+                         'tlp5_v83': ('tlp5_v83', 'thelittleprince/pretrained_5players.pt', dict(tlp_players=5), 'TLPGame', 'TLPGame', 128),
                          # AbaloneNNet.py nn_version 21 (Belgian Daisy, the layout the engine plays): a 2-d MobileNet on the 9 x 9 grid,
                          # torchvision InvertedResidual blocks (the refshim stand-in); engine net through nn_abalone.hip.h
                          'abalone_v21': ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict(), 'AbaloneGame', 'AbaloneGame', 128),
