@@ -63,7 +63,7 @@ class Coach:
             from . import train as _train
             engine_module = isinstance(nnet, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
                                                    _train.AbaloneV21Module, _train.SmallworldV62Module, _train.AkropolisV31Module,
-                                                   _train.MinivillesV82Module, _train.TLPV83Module))
+                                                   _train.MinivillesV82Module, _train.TLPV83Module, _train.BotanikV10Module))
             w = NNetWrapper(game, dict(nn_version=getattr(nnet, 'version', -1), learn_rate=_get(args, 'learn_rate', 3e-3),
                                        batch_size=_get(args, 'batch_size', 512), epochs=_get(args, 'epochs', 2),
                                        q_weight=_get(args, 'q_weight', 0.5), dropout=_get(args, 'dropout', 0.0)),

@@ -20,6 +20,7 @@
 #include "nn_abalone.hip.h"
 #include "nn_smallworld.hip.h"
 #include "nn_akropolis.hip.h"
+#include "nn_botanik.hip.h"
 
 using namespace azg;
 
@@ -520,6 +521,30 @@ extern "C" int azg_nn_akr31_forward(const int8_t* boards, const uint8_t* valid, 
     else k_akr31_net<4><<<dim3(B), dim3(AKR_THREADS), 0, st>>>(w[0], w[1], w[2], boards, valid, pi, v);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// ---- Botanik nets V10 / V11 (1-d branch + 1 or 2 machine branches, A = 428, P = 2): one launch, 8 samples per workgroup (nn_botanik.hip.h) ----
+template <int NM>
+static int bot_launch(const BotNetW& N, const int8_t* boards, const uint8_t* valid, int B, float* pi, float* v, hipStream_t s) {
+    static bool attr = false;
+    if (!attr) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_bot_net<NM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BOT_LDS));
+        attr = true;
+    }
+    k_bot_net<NM><<<dim3((B + BOT_NS - 1) / BOT_NS), dim3(BOT_THREADS), BOT_LDS, s>>>(N, boards, valid, B, pi, v);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int azg_nn_bot_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_mach, int P, int A, int B,
+                                  float* pi, float* v, void* stream) {
+    if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_bot_forward: null/empty argument");
+    if ((n_mach != 1 && n_mach != 2) || P != 2 || A != BOT_A)
+        return fail("azg_nn_bot_forward: built for n_mach 1 (nn_version 10) or 2 (nn_version 11), P = 2, A = 428");
+    for (int i = 0; i < 10; i++)
+        if (!w[i]) return fail("azg_nn_bot_forward: null weight pointer");
+    BotNetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9]};
+    return n_mach == 1 ? bot_launch<1>(N, boards, valid, B, pi, v, (hipStream_t)stream) : bot_launch<2>(N, boards, valid, B, pi, v, (hipStream_t)stream);
 }
 
 extern "C" int azg_nn_board_to_x_ld(const int8_t* boards, float* x, int B, int C, int L, int ldx, void* stream) {

@@ -1543,6 +1543,220 @@ class AkropolisV31Hip:
         return pi[0].cpu().numpy(), v[0].cpu().numpy()
 
 
+class BotanikV1x:
+    """botanik/BotanikNNet.py nn_version 10 (:105-160) and 11 (:162-237), forward :251-292: the (66, 5, 7) board, rows 0..25 read.
+    1-d branch: rows 0..5 as (C = 7, L = 30) -> first_layer_1d (Linear 7 -> 7 + BN) -> trunk_1d InvertedResidual1d(7, 21, 7, 30, ReLU, SE
+    avg: the reference passes "RE" as use_se, which is truthy) -> per head InvertedResidual1d(7, 21, 7, 30, Hardswish, SE max) + Flatten +
+    Linear(210, 428 | 2).  Machine branch (mach0; V11 also mach1, separate weights): the first 343 bytes of rows 6..15 (16..25) as
+    (H, W, C) = (7, 7, 7) -> conv3x3 7 -> 16 -> one torchvision InvertedResidual 16 -> 32 -> 16 (ReLU, no SE) -> per head three
+    InvertedResidual 16 -> 48 -> 16 (Hardswish, SE) + Flatten + Linear(784, 428 | 2).  The branch outputs are summed, then
+    final_layers_PI (428 -> 428 + ReLU -> 428), masked softmax; final_layers_V (2 -> 2 + ReLU -> 2), tanh.  The version is 11 when the
+    state_dict has first_layer_mach1.weight.  BatchNorm (eps 1e-5) folded; plain torch ops."""
+    A, P = 428, 2
+
+    def __init__(self, state_dict, device='cuda:0', dtype=torch.float32):
+        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        self.n_mach = 2 if 'first_layer_mach1.weight' in sd else 1
+        self.version = 9 + self.n_mach
+        t = {}
+
+        def lin_bn(pre):                 # LinearNormActivation: Linear (no bias) + BatchNorm1d over its outputs
+            s, b = _fold_bn(sd, pre + '.norm')
+            return sd[pre + '.linear.weight'] * s[:, None], b
+        t['1d.W0'], t['1d.b0'] = lin_bn('first_layer_1d')
+        for j, pre in enumerate(('trunk_1d.0', 'output_layers_PI_1d.0', 'output_layers_V_1d.0')):
+            k = '1d.%d.' % j
+            t[k + 'We'], t[k + 'be'] = lin_bn(pre + '.expand')
+            t[k + 'sd'], t[k + 'bd'] = _fold_bn(sd, pre + '.depthwise.norm')
+            t[k + 'Wt'] = sd[pre + '.depthwise.linear.weight']
+            for n in ('1', '2'):
+                t[k + 'W' + n], t[k + 'b' + n] = sd[pre + '.se.fc%s.weight' % n], sd[pre + '.se.fc%s.bias' % n]
+            t[k + 'Wp'], t[k + 'bp'] = lin_bn(pre + '.project')
+        for h, pre in (('pi', 'output_layers_PI'), ('v', 'output_layers_V')):
+            t[h + '1d.W'], t[h + '1d.b'] = sd[pre + '_1d.2.weight'], sd[pre + '_1d.2.bias']
+
+        def conv_bn(pre):
+            s, b = _fold_bn(sd, pre + '.1')
+            return sd[pre + '.0.weight'] * s[:, None, None, None], b
+        for m in range(self.n_mach):
+            k = 'm%d.' % m
+            t[k + 'c0'] = sd['first_layer_mach%d.weight' % m]
+            for j, n in enumerate(('e', 'd', 'p')):
+                t[k + 't.w' + n], t[k + 't.b' + n] = conv_bn('trunk_mach%d.0.block.%d' % (m, j))
+            for h, pre in enumerate(('output_layers_PI_mach%d' % m, 'output_layers_V_mach%d' % m)):
+                for b in range(3):
+                    q, blk = k + 'h%d.' % (3 * h + b), '%s.%d.block.' % (pre, b)
+                    t[q + 'we'], t[q + 'be'] = conv_bn(blk + '0')
+                    t[q + 'wd'], t[q + 'bd'] = conv_bn(blk + '1')
+                    for n in ('1', '2'):
+                        t[q + 'w' + n], t[q + 'b' + n] = sd[blk + '2.fc%s.weight' % n], sd[blk + '2.fc%s.bias' % n]
+                    t[q + 'wp'], t[q + 'bp'] = conv_bn(blk + '3')
+                t[('pi' if h == 0 else 'v') + k + 'W'], t[('pi' if h == 0 else 'v') + k + 'b'] = sd[pre + '.4.weight'], sd[pre + '.4.bias']
+        for n, pre in (('f1', 'final_layers_PI.0'), ('f2', 'final_layers_PI.2'), ('fv1', 'final_layers_V.0'), ('fv2', 'final_layers_V.2')):
+            t[n + '.W'], t[n + '.b'] = sd[pre + '.weight'], sd[pre + '.bias']
+        self.t = {k: v.contiguous() for k, v in t.items()}
+        self.to(device, dtype)
+
+    def to(self, device, dtype=torch.float32):
+        self.device, self.dtype = torch.device(device), dtype
+        self.t = {k: v.to(self.device, dtype) for k, v in self.t.items()}
+        return self
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        z = np.load(path)
+        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
+
+    def _block1d(self, k, x, hs, maxpool):              # x [B, 7, 30]
+        t, act = self.t, (F.hardswish if hs else F.relu)
+        h = act(torch.einsum('ec,bcl->bel', t[k + 'We'], x) + t[k + 'be'][:, None])
+        h = act(torch.matmul(h, t[k + 'Wt'].t()) * t[k + 'sd'][:, None] + t[k + 'bd'][:, None])
+        p = h.amax(dim=2) if maxpool else h.mean(dim=2)
+        s = F.hardsigmoid(F.linear(F.relu(F.linear(p, t[k + 'W1'], t[k + 'b1'])), t[k + 'W2'], t[k + 'b2']))
+        return torch.einsum('ce,bel->bcl', t[k + 'Wp'], h * s[:, :, None]) + t[k + 'bp'][:, None] + x
+
+    def _block2d(self, q, x):                          # torchvision InvertedResidual 16 -> 48 -> 16, Hardswish, SE
+        t = self.t
+        h = F.hardswish(F.conv2d(x, t[q + 'we'], t[q + 'be']))
+        h = F.hardswish(F.conv2d(h, t[q + 'wd'], t[q + 'bd'], padding=1, groups=h.shape[1]))
+        s = F.hardsigmoid(F.conv2d(F.relu(F.conv2d(F.adaptive_avg_pool2d(h, 1), t[q + 'w1'], t[q + 'b1'])), t[q + 'w2'], t[q + 'b2']))
+        return F.conv2d(h * s, t[q + 'wp'], t[q + 'bp']) + x
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        t, B = self.t, boards.shape[0]
+        x = boards.reshape(B, 66, 5, 7).to(self.dtype)
+        x1 = torch.einsum('oc,bcl->bol', t['1d.W0'], x[:, :6].permute(0, 3, 1, 2).flatten(2)) + t['1d.b0'][:, None]
+        x1 = self._block1d('1d.0.', x1, False, False)
+        pi = F.linear(self._block1d('1d.1.', x1, True, True).flatten(1), t['pi1d.W'], t['pi1d.b'])
+        v = F.linear(self._block1d('1d.2.', x1, True, True).flatten(1), t['v1d.W'], t['v1d.b'])
+        for m in range(self.n_mach):
+            k = 'm%d.' % m
+            xm = x[:, 6 + 10 * m:16 + 10 * m].flatten(1)[:, :343].reshape(B, 7, 7, 7).permute(0, 3, 1, 2)
+            xm = F.conv2d(xm, t[k + 'c0'], padding=1)
+            h = F.relu(F.conv2d(xm, t[k + 't.we'], t[k + 't.be']))
+            h = F.relu(F.conv2d(h, t[k + 't.wd'], t[k + 't.bd'], padding=1, groups=h.shape[1]))
+            xm = F.conv2d(h, t[k + 't.wp'], t[k + 't.bp']) + xm
+            for hd in range(2):
+                y = xm
+                for b in range(3):
+                    y = self._block2d(k + 'h%d.' % (3 * hd + b), y)
+                if hd == 0:
+                    pi = pi + F.linear(y.flatten(1), t['pi' + k + 'W'], t['pi' + k + 'b'])
+                else:
+                    v = v + F.linear(y.flatten(1), t['v' + k + 'W'], t['v' + k + 'b'])
+        logits = F.linear(F.relu(F.linear(pi, t['f1.W'], t['f1.b'])), t['f2.W'], t['f2.b']).float()
+        v = torch.tanh(F.linear(F.relu(F.linear(v, t['fv1.W'], t['fv1.b'])), t['fv2.W'], t['fv2.b']).float())
+        logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
+        return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
+        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+class BotanikV1xHip:
+    """BotanikV1x (V10 or V11, A = 428) evaluated by the engine's one-launch kernel (azg_nn_bot_forward, csrc/nn_botanik.hip.h: the
+    1-d branch on the vector ALUs, the machine branches' 1x1 convolutions and every policy Linear as f32 MFMA GEMMs, the depthwise 3x3 on
+    the vector ALUs, final layers, masked softmax and tanh in the same launch).  Wraps a BotanikV1x; static pi / v buffers (HIP-graph
+    capture of the engine's rounds)."""
+    MBLOB = 24496
+
+    def __init__(self, base, max_batch=4096):
+        import ctypes as C
+        from . import _lib
+        self._lib, self.base, self.device = _lib, base, base.device
+        self.P, self.A, self.n_mach = base.P, base.A, base.n_mach
+        assert base.dtype == torch.float32 and self.device.type == 'cuda'
+        self._keep = self.pack(base)
+        self.ptrs = (C.c_void_p * 10)(*[t.data_ptr() for t in self._keep])
+        self._alloc(max_batch)
+
+    @staticmethod
+    def frag(m, G, nct):
+        """[K][N] -> [nct][G][64]: element m[G * (lane >> 4) + j][16 ct + (lane & 15)] (zero padded): the VGPR-resident fragments"""
+        z = torch.zeros((4 * G, 16 * nct), dtype=torch.float32, device=m.device)
+        z[:m.shape[0], :m.shape[1]] = m
+        return z.view(4, G, nct, 16).permute(2, 1, 0, 3).contiguous().view(-1)
+
+    @staticmethod
+    def sfrag(m, KQ):
+        """[K][N <= 432] -> [27][KQ][64]: element m[4 j + (lane >> 4)][16 ct + (lane & 15)] (zero padded): the streamed FC fragments"""
+        z = torch.zeros((4 * KQ, 432), dtype=torch.float32, device=m.device)
+        z[:m.shape[0], :m.shape[1]] = m
+        return z.view(KQ, 4, 27, 16).permute(2, 0, 1, 3).contiguous().view(-1)
+
+    @classmethod
+    def pack(cls, base):
+        """the 10 weight tensors of azg_nn_bot_forward (include/azg.h), on base's device"""
+        t, d, M = base.t, base.device, range(base.n_mach)
+        cat = lambda ts: torch.cat([x.reshape(-1) for x in ts]).contiguous()  # noqa: E731
+        w1d = [t['1d.W0'], t['1d.b0']]
+        for j in range(3):
+            w1d += [t['1d.%d.%s' % (j, n)] for n in ('We', 'be', 'Wt', 'sd', 'bd', 'W1', 'b1', 'W2', 'b2', 'Wp', 'bp')]
+        wm = []
+        for m in M:
+            k = 'm%d.' % m
+            wm += [cls.frag(t[k + 'c0'].permute(2, 3, 1, 0).reshape(63, 16), 16, 1),
+                   cls.frag(t[k + 't.we'].reshape(32, 16).t(), 4, 2), t[k + 't.be'], t[k + 't.wd'].reshape(32, 9).t(), t[k + 't.bd'],
+                   cls.frag(t[k + 't.wp'].reshape(16, 32).t(), 8, 1), t[k + 't.bp']]
+            for b in range(6):
+                q = k + 'h%d.' % b
+                wm += [cls.frag(t[q + 'we'].reshape(48, 16).t(), 4, 3), t[q + 'be'], t[q + 'wd'].reshape(48, 9).t(), t[q + 'bd'],
+                       t[q + 'w1'].reshape(16, 48), t[q + 'b1'], t[q + 'w2'].reshape(48, 16), t[q + 'b2'],
+                       cls.frag(t[q + 'wp'].reshape(16, 48).t(), 12, 1), t[q + 'bp']]
+        wpi = [cls.sfrag(t['pi1d.W'].t(), 53)] + [cls.sfrag(t['pim%d.W' % m].t(), 196) for m in M]
+        bpi = torch.zeros(432, dtype=torch.float32, device=d)
+        bpi[:428] = t['pi1d.b'] + sum(t['pim%d.b' % m] for m in M)
+        bf1, bf2 = torch.zeros(432, dtype=torch.float32, device=d), torch.zeros(432, dtype=torch.float32, device=d)
+        bf1[:428], bf2[:428] = t['f1.b'], t['f2.b']
+        tail = [t['v1d.b'] + sum(t['vm%d.b' % m] for m in M), t['fv1.W'], t['fv1.b'], t['fv2.W'], t['fv2.b']]
+        keep = [cat(w1d), cat(wm), cat(wpi), bpi, cat([t['v1d.W']] + [t['vm%d.W' % m] for m in M]),
+                cls.sfrag(t['f1.W'].t(), 108), bf1, cls.sfrag(t['f2.W'].t(), 108), bf2, cat(tail)]
+        assert keep[0].numel() == 56 + 3 * 1629 and keep[1].numel() == cls.MBLOB * base.n_mach and keep[9].numel() == 14
+        return keep
+
+    def _alloc(self, B):
+        self.maxB = B
+        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+
+    def clone_buffers(self):
+        import copy
+        other = copy.copy(self)
+        other._alloc(self.maxB)
+        return other
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        import ctypes as C
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        boards = boards.reshape(B, -1)
+        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 2310
+        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+        assert valids.shape == (B, self.A) and valids.is_cuda
+        self._lib.check(self._lib.lib().azg_nn_bot_forward(p(boards), p(valids), self.ptrs, self.n_mach, self.P, self.A, B, p(self.pi),
+                                                           p(self.v), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return self.pi[:B], self.v[:B]
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
 class TorchModuleEvaluator:
     """Leaf evaluator around ANY torch module with the reference's forward signature
     `module(board f32[B, *board_shape], valid_actions bool[B, A]) -> (log_pi f32[B, A], v f32[B, P])` -- the torch branch of

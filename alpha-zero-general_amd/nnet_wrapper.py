@@ -25,7 +25,7 @@ from . import _lib, nnet as _nn, train as _train
 
 # nn_version -> trainable module per game (splendor/SplendorNNet.py V80, azul/AzulNNet.py V84, santorini/SantoriniNNet.py V89/V78,
 # abalone/AbaloneNNet.py V21, smallworld/SmallworldNNet.py V62, akropolis/AkropolisNNet.py V31, minivilles/MinivillesNNet.py V82,
-# thelittleprince/TLPNNet.py V83)
+# thelittleprince/TLPNNet.py V83, botanik/BotanikNNet.py V10 / V11)
 _DEFAULT_VERSION = {(_lib.SPLENDOR, 2): 80, (_lib.SPLENDOR, 3): 80, (_lib.SPLENDOR, 4): 80, (_lib.AZUL, 2): 84,
                     (_lib.SANTORINI, 1): 89, (_lib.SANTORINI, 11): 78}
 
@@ -50,8 +50,10 @@ def _module_for(game, version, dropout):
         return _train.MinivillesV82Module(P, A, dropout)
     if gid == _lib.TLP and version == 83:
         return _train.TLPV83Module(P, A, dropout)
+    if gid == _lib.BOTANIK and version in (10, 11):
+        return (_train.BotanikV10Module if version == 10 else _train.BotanikV11Module)(P, A, dropout)
     raise ValueError('nn_version %r is not built for this game (engine nets: Splendor 80, Azul 84, Santorini 89 no-gods / 78 with gods, '
-                     'Abalone 21, Smallworld 62, Akropolis 31, Minivilles 82, The Little Prince 83)'
+                     'Abalone 21, Smallworld 62, Akropolis 31, Minivilles 82, The Little Prince 83, Botanik 10 / 11)'
                      % (version,))
 
 
@@ -61,8 +63,10 @@ def evaluator_for(module, game, max_batch):
     dev, ver = str(game.device), getattr(module, 'version', 80)
     if not isinstance(module, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
                                _train.AbaloneV21Module, _train.SmallworldV62Module, _train.AkropolisV31Module, _train.MinivillesV82Module,
-                               _train.TLPV83Module)):
+                               _train.TLPV83Module, _train.BotanikV10Module)):
         return _nn.TorchModuleEvaluator(module, game, max_batch)
+    if isinstance(module, _train.BotanikV10Module):                 # V10 and its subclass V11
+        return _nn.BotanikV1xHip(_nn.BotanikV1x(sd, device=dev), max_batch=max_batch)
     if isinstance(module, (_train.MinivillesV82Module, _train.TLPV83Module)):
         return _nn.MobileNet1dHip(_nn.MobileNet1d(sd, num_players=game.P, device=dev), max_batch=max_batch)
     if ver == 31:

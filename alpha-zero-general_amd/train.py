@@ -398,6 +398,70 @@ class AkropolisV31Module(nn.Module):
         return F.log_softmax(pi, dim=1), torch.tanh(v)
 
 
+class _MBBlock2dSE(nn.Module):
+    """torchvision's MobileNetV3 InvertedResidual with a 3x3 depthwise, SE and Hardswish, as BotanikNNet.py:127-137 configures the head
+    blocks (16 -> 48 -> 16, squeeze 16, residual).  Parameter names block.{0,1,3}.{0 conv, 1 BatchNorm}, block.2.fc{1,2}"""
+
+    def __init__(self, c, e):
+        super().__init__()
+        cna = lambda i, o, k, g, act: nn.Sequential(nn.Conv2d(i, o, k, padding=(k - 1) // 2, groups=g, bias=False),  # noqa: E731
+                                                    nn.BatchNorm2d(o), *([nn.Hardswish()] if act else []))
+        self.block = nn.Sequential(cna(c, e, 1, 1, True), cna(e, e, 3, e, True), _SqueezeExcitation2d(e, _make_divisible(e // 4, 8)),
+                                   cna(e, c, 1, 1, False))
+
+    def forward(self, x):
+        return self.block(x) + x
+
+
+class BotanikV10Module(nn.Module):
+    """botanik/BotanikNNet.py nn_version 10 (:105-160, forward :251-273) with the reference's parameter names: the 1-d branch
+    (first_layer_1d, trunk_1d, output_layers_{PI,V}_1d) on rows 0..5 and one machine branch (first_layer_mach0, trunk_mach0,
+    output_layers_{PI,V}_mach0) on rows 6..15, summed into final_layers_PI / final_layers_V.  In training mode the trunk_1d output goes
+    through dropout, as in the reference (:256)."""
+    version = 10
+    N_MACH = 1
+
+    def __init__(self, num_players=2, action_size=428, dropout=0.0):
+        super().__init__()
+        self.P, self.A, self.dropout = num_players, action_size, dropout
+        self.first_layer_1d = _LinearNormAct(7, 7, None)
+        self.trunk_1d = nn.Sequential(_Block(7, 21, False, 'avg', tokens=30))
+        self.output_layers_PI_1d = nn.Sequential(_Block(7, 21, True, 'max', tokens=30), nn.Flatten(1), nn.Linear(210, action_size))
+        self.output_layers_V_1d = nn.Sequential(_Block(7, 21, True, 'max', tokens=30), nn.Flatten(1), nn.Linear(210, num_players))
+        for m in range(self.N_MACH):
+            setattr(self, 'first_layer_mach%d' % m, nn.Conv2d(7, 16, 3, padding=1, bias=False))
+            setattr(self, 'trunk_mach%d' % m, nn.Sequential(_MBBlock2d(16, 32)))
+            setattr(self, 'output_layers_PI_mach%d' % m, nn.Sequential(*[_MBBlock2dSE(16, 48) for _ in range(3)], nn.Flatten(1),
+                                                                      nn.Linear(784, action_size)))
+            setattr(self, 'output_layers_V_mach%d' % m, nn.Sequential(*[_MBBlock2dSE(16, 48) for _ in range(3)], nn.Flatten(1),
+                                                                     nn.Linear(784, num_players)))
+        self.final_layers_PI = nn.Sequential(nn.Linear(action_size, action_size), nn.ReLU(), nn.Linear(action_size, action_size))
+        self.final_layers_V = nn.Sequential(nn.Linear(num_players, num_players), nn.ReLU(), nn.Linear(num_players, num_players))
+        self.register_buffer('lowvalue', torch.FloatTensor([-1e8]))
+
+    def forward(self, boards, valid_actions):
+        x = boards.reshape(-1, 66, 5, 7).float()
+        B = x.shape[0]
+        x1 = self.first_layer_1d(x[:, :6].permute(0, 3, 1, 2).flatten(2))
+        x1 = F.dropout(self.trunk_1d(x1), p=self.dropout, training=self.training)
+        pi, v = self.output_layers_PI_1d(x1), self.output_layers_V_1d(x1)
+        for m in range(self.N_MACH):
+            xm = x[:, 6 + 10 * m:16 + 10 * m].flatten(1)[:, :343].reshape(B, 7, 7, 7).permute(0, 3, 1, 2)
+            xm = getattr(self, 'trunk_mach%d' % m)(getattr(self, 'first_layer_mach%d' % m)(xm))
+            pi = pi + getattr(self, 'output_layers_PI_mach%d' % m)(xm)
+            v = v + getattr(self, 'output_layers_V_mach%d' % m)(xm)
+        v = self.final_layers_V(v)
+        pi = torch.where(valid_actions.bool(), self.final_layers_PI(pi), self.lowvalue)
+        return F.log_softmax(pi, dim=1), torch.tanh(v)
+
+
+class BotanikV11Module(BotanikV10Module):
+    """botanik/BotanikNNet.py nn_version 11 (:162-237, forward :274-289): V10 plus a second machine branch with its own weights
+    (first_layer_mach1, trunk_mach1, output_layers_{PI,V}_mach1) on rows 16..25"""
+    version = 11
+    N_MACH = 2
+
+
 def loss_pi(target_pi, out_log_pi):                                            # GenericNNetWrapper.py:179-181
     return F.kl_div(out_log_pi, target_pi, reduction='batchmean')
 

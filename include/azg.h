@@ -487,6 +487,24 @@ int azg_nn_sw62_forward(const int8_t* boards_dev, const uint8_t* valid_dev, cons
    f32 operands, f32 accumulation (the policy dot products in f64).  (P, A) must be (2, 4056), (3, 5070) or (4, 6084). */
 int azg_nn_akr31_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int P, int A, int B, float* pi_dev,
                          float* v_dev, void* stream);
+/* The Botanik nets (nn_version 10: botanik/BotanikNNet.py:105-160, 11: :162-237, forward :251-292): ONE launch on `stream`, 8 samples per
+   workgroup (nn_botanik.hip.h).  boards int8 [B][66][5][7] (rows 0..25 read), valid u8 [B][428] -> pi f32 [B][428] (masked softmax),
+   v f32 [B][2] (tanh).  n_mach = 1 (V10: the 1-d branch and mach0) or 2 (V11: and mach1).  Every BatchNorm folded; f32; the fragment
+   element F[k][n] of a [nct][G][64] array sits at lane (n & 15) + 16 * (k / G) of slot (ct, k % G) ("k = G g + m") or, for the streamed
+   FC fragments [27][KQ][64], at lane (n & 15) + 16 * (k % 4) of slot (ct, k / 4) ("k = 4 j + g").  w = 10 device pointers:
+     w[0] W1d   first_layer_1d W [7][7] (out, in), b [7]; then trunk_1d, output_layers_PI_1d.0, output_layers_V_1d.0, 1629 floats each:
+                We [21][7], be [21], Wt [30][30] (depthwise Linear, out, in), sd, bd [21] (its BN), W1 [8][21], b1 [8], W2 [21][8], b2 [21]
+                (SE), Wp [7][21], bp [7]
+     w[1] Wm    per machine branch 24496 floats: first conv [16][64] (k = 16 g + m, k = tap*7 + c < 63); trunk We [2][4][64], be [32],
+                Wd [9][32] (tap-major), bd [32], Wp [1][8][64], bp [16]; six SE blocks (policy head 0..2, value head 0..2) of 3680:
+                We [3][4][64], be [48], Wd [9][48], bd [48], W1 [16][48], b1 [16], W2 [48][16], b2 [48], Wp [1][12][64], bp [16]
+     w[2] Wpi   the branch policy Linears stacked along K: [27][53][64] (1-d, K 210 padded to 212), then [27][196][64] per branch
+     w[3] bpi   [432] their biases summed; w[4] Wv: the branch value Linears, [2][210] then [2][784] per branch
+     w[5..8]    final_layers_PI.0 / .2: [27][108][64] (K and N padded to 432), bias [432] each
+     w[9] tail  [14]: the branch value biases summed [2], final_layers_V.0 W [2][2], b [2], final_layers_V.2 W [2][2], b [2]
+   Same 1e-5 contract as the torch net.  n_mach must be 1 or 2, P 2, A 428. */
+int azg_nn_bot_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_mach, int P, int A, int B,
+                       float* pi_dev, float* v_dev, void* stream);
 /* boards int8 [B][C][7] (reference board layout) -> x f32 [B][7][C] */
 int azg_nn_board_to_x(const int8_t* boards_dev, float* x_dev, int B, int C, void* stream);
 /* boards int8 [B][C][L] -> x f32 [B][L][ldx], columns C..ldx-1 zeroed (row stride padded to a multiple of 4 floats) */

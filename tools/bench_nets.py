@@ -1,5 +1,6 @@
 """µs per forward at T leaves for every evaluation path of the MobileNet-1d nets, the Santorini nets, the Abalone net, the Smallworld
-nets and the Akropolis nets (HIP events, 50 forwards after warm-up), and the shipped MobileNet-1d checkpoints of every player count."""
+nets, the Akropolis nets and the Botanik nets (HIP events, 50 forwards after warm-up), and the shipped MobileNet-1d checkpoints of every
+player count."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
@@ -133,3 +134,32 @@ for tag in ('splendor3_v80', 'minivilles3_v82', 'minivilles4_v82', 'tlp4_v83', '
           ' k_mb1d_net h2 %.1f us' % th2,
           ' floors: %.2f MFLOP/sample = %.1f us at the f32 peak, %.1f MB = %.1f us at 8 TB/s;  h2 kernel at %.0f %% of the %s floor'
           % (2e-6 * mac, t_flop, hbm / 1e6, t_hbm, 100 * max(t_flop, t_hbm) / th2, 'compute' if t_flop >= t_hbm else 'HBM'), flush=True)
+
+# Botanik V10 / V11 (no checkpoint: the stand-in weights of weightstats_botanik_v1x.npz) at T: the plain-torch net, the one-launch kernel
+# and the trainable module through TorchModuleEvaluator, on the fixture boards tiled to T.  Floors from shapes: multiply-adds per sample
+# (1-d branch: first layer 30*7*7, per block 2*30*7*21 + 30*30*21 + 2*21*8, FC 210*430; per machine branch: conv 49*63*16, trunk
+# 2*49*16*32 + 49*32*9, six head blocks 2*49*16*48 + 49*48*9 + 2*48*16, FC 784*430; final 2*428^2 + 2*2^2) at the f32 peak (157.3 TF),
+# and the HBM bytes (f32 weights once, int8 boards, u8 valid, f32 pi and v) at 8 TB/s; the kernel's share is the larger floor over its time.
+for version in (10, 11):
+    from azg_amd import formats
+    tag = 'botanik_v%d' % version
+    sd = formats.fixture_state_dict(G, tag)[0]
+    base = nnet.BotanikV1x(sd, device='cuda:0')
+    M = base.n_mach
+    mac = 30 * 49 + 3 * (2 * 30 * 7 * 21 + 30 * 30 * 21 + 2 * 21 * 8) + 210 * 430 \
+        + M * (49 * 63 * 16 + 2 * 49 * 16 * 32 + 49 * 32 * 9 + 6 * (2 * 49 * 16 * 48 + 49 * 48 * 9 + 2 * 48 * 16) + 784 * 430) + 2 * 428 * 428 + 8
+    n_w = sum(int(np.prod(v.shape)) for v in sd.values())
+    t_flop = 2.0 * mac * T / 157.3e12 * 1e6
+    hbm = 4 * n_w + (2310 + 428 + 4 * 428 + 8) * T
+    t_hbm = hbm / 8.0e12 * 1e6
+    d = np.load(G + '/netfwd_%s.npz' % tag)
+    idx = np.arange(T) % len(d['boards'])
+    boards = torch.from_numpy(d['boards'][idx].reshape(T, -1)).to('cuda:0')
+    valids = torch.from_numpy(d['masks'][idx]).to('cuda:0')
+    mod = (train.BotanikV10Module if version == 10 else train.BotanikV11Module)()
+    mod.load_state_dict({k: torch.as_tensor(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    t_k = timed(nnet.BotanikV1xHip(base, max_batch=T), boards, valids)
+    print('botanik V%d T=%d' % (version, T), 'torch ops %.1f us' % timed(base, boards, valids.bool(), 10), ' k_bot_net %.1f us' % t_k,
+          ' TorchModuleEvaluator %.1f us' % timed(nnet.TorchModuleEvaluator(mod, games.BotanikGame()), boards, valids, 10),
+          ' floors: %.2f MFLOP/sample = %.1f us at the f32 peak, %.1f MB = %.1f us at 8 TB/s;  kernel at %.0f %% of the %s floor'
+          % (2e-6 * mac, t_flop, hbm / 1e6, t_hbm, 100 * max(t_flop, t_hbm) / t_k, 'compute' if t_flop >= t_hbm else 'HBM'), flush=True)

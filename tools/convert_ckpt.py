@@ -1,6 +1,7 @@
 """Convert a reference checkpoint (.pt with pickled full_model, needs torchvision) into plain tensors + MCTS args, and
 record net-forward golden vectors (G4) from the reference's own model.  Build-container only.
     python tools/convert_ckpt.py
+    python tools/convert_ckpt.py --botanik          (the Botanik stand-in fixtures, below)
 writes tests/golden/weights_splendor2_v80.npz (state_dict tensors + embedded MCTS args, DATA only) and
        tests/golden/netfwd_splendor2_v80.npz (256 boards/masks -> the reference model's pi, v)."""
 import os
@@ -140,6 +141,72 @@ F64 = [('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_player
        ('akropolis4_v31', 'akropolis/pretrained_4pl.pt', dict(akropolis_players=4))]
 
 
+# ---- Botanik (botanik/BotanikNNet.py nn_version 10 :105-160, 11 :162-237): the reference ships no checkpoint (pretrained.pt is not in
+# its snapshot), so the fixtures are stand-ins built the same way as Minivilles 4p's: the per-tensor statistics of the reference module's
+# own fresh init (weightstats_botanik_v1x.npz, formats.weight_stats), with the spreads below given to the tensors its init leaves
+# constant -- BatchNorm weights 1, biases 0, running means 0, running variances 1 and the zero-initialised Linear biases -- so that every
+# BatchNorm fold and bias sum is exercised.  The reference module is then evaluated on the drawn weights (loaded with strict=True).
+# Its 2-d blocks are torchvision's InvertedResidual: here the refshim stand-in written from the published block.
+BOT_SPREAD = {'bn_weight': (1.0, 0.2), 'bn_bias': (0.0, 0.1), 'bn_running_mean': (0.0, 0.1), 'bn_log_running_var': (0.0, 0.3), 'bias': (0.0, 0.05)}
+
+
+def _botanik_stats(sd, version):
+    from azg_amd import formats
+    out = formats.weight_stats(sd, seed=version)
+    bn = {k.rsplit('.', 1)[0] for k in sd if k.endswith('running_var')}
+    for k in sd:
+        if 'shape/' + k not in out or '.' not in k:        # integer counters; the lowvalue buffer
+            continue
+        mod, leaf = k.rsplit('.', 1)
+        if mod in bn:
+            out['stat/' + k] = np.array(BOT_SPREAD['bn_log_running_var' if leaf == 'running_var' else 'bn_' + leaf])
+        elif leaf == 'bias':
+            out['stat/' + k] = np.array(BOT_SPREAD['bias'])
+    out['arg/nn_version'] = np.array(version)
+    return out
+
+
+def botanik(version, n_vec=128, n_rand=16):
+    """weightstats_botanik_v<version>.npz, netfwd_ (f32), netfwd64_ (f64) and netfwdrand_ (random int8 boards, all-valid masks, f32 and
+    f64) from the reference's BotanikNNet on the stand-in weights"""
+    import importlib
+    import torch
+    sys.path.insert(0, os.path.join(HERE, '..'))
+    from azg_amd import formats
+    m = H.load_reference()
+    BN = importlib.import_module('botanik.BotanikNNet')
+    g = m['BotanikGame'].BotanikGame()
+    torch.manual_seed(version)
+    model = BN.BotanikNNet(g, dict(nn_version=version, dropout=0.3)).eval()
+    tag = 'botanik_v%d' % version
+    stats = _botanik_stats({k: v.numpy() for k, v in model.state_dict().items()}, version)
+    np.savez_compressed(os.path.join(GOLDEN, 'weightstats_%s.npz' % tag), **stats)
+    sd = formats.synthetic_state_dict(np.load(os.path.join(GOLDEN, 'weightstats_%s.npz' % tag)))
+    model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, strict=True)
+    env = np.load(os.path.join(GOLDEN, 'env_botanik.npz'))
+    sel = np.random.default_rng(0).choice(len(env['canonical']), size=min(n_vec, len(env['canonical'])), replace=False)
+    shape, A = tuple(g.getBoardSize()), g.getActionSize()
+    boards = env['canonical'][sel].reshape((-1,) + shape)
+    masks = np.array([g.getValidMoves(b, 0) for b in boards]).astype(np.uint8)
+    rboards = np.random.default_rng(1).integers(-128, 128, size=(n_rand,) + shape).astype(np.int8)
+    rmasks = np.ones((n_rand, A), dtype=np.uint8)
+    with torch.no_grad():
+        out = [model(torch.from_numpy(b.astype(np.float32)), torch.from_numpy(k.astype(bool))) for b, k in ((boards, masks), (rboards, rmasks))]
+        model = model.double()
+        out64 = [model(torch.from_numpy(b.astype(np.float64)), torch.from_numpy(k.astype(bool))) for b, k in ((boards, masks), (rboards, rmasks))]
+    (lp, v), (rlp, rv) = out
+    (lp64, v64), (rlp64, rv64) = out64
+    np.savez_compressed(os.path.join(GOLDEN, 'netfwd_%s.npz' % tag), boards=boards.astype(np.int8), masks=masks, pi=torch.exp(lp).numpy(),
+                        v=v.numpy())
+    np.savez_compressed(os.path.join(GOLDEN, 'netfwd64_%s.npz' % tag), pi64=torch.exp(lp64).numpy(), v64=v64.numpy())
+    np.savez_compressed(os.path.join(GOLDEN, 'netfwdrand_%s.npz' % tag), boards=rboards, masks=rmasks, pi=torch.exp(rlp).numpy(),
+                        v=rv.numpy(), pi64=torch.exp(rlp64).numpy(), v64=rv64.numpy())
+    for name, a, b in (('game', (torch.exp(lp), v), (torch.exp(lp64), v64)), ('random', (torch.exp(rlp), rv), (torch.exp(rlp64), rv64))):
+        print('%-12s %-6s boards |ref_f32 - ref_f64|: pi %.3g  v %.3g' % (tag, name, (a[0].double() - b[0]).abs().max(),
+                                                                          (a[1].double() - b[1]).abs().max()))
+    H.cleanup()
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == '--f64':
         # `--f64` rewrites every netfwd64_*.npz; `--f64 TAG...` only those of the tags given
@@ -152,6 +219,11 @@ def main():
         for name, ckpt_rel, load_kw in F64:
             if name in sys.argv[2:]:
                 forward_random(name, ckpt_rel, load_kw)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == '--botanik':
+        # `--botanik`: the stand-in fixtures of both Botanik versions (no checkpoint: see BOT_SPREAD)
+        for version in (10, 11):
+            botanik(version)
         return
     if len(sys.argv) > 2 and sys.argv[1] == '--only':
         return convert(*{'santorini11_v78': ('santorini11_v78', 'santorini/pretrained_withgods.pt', dict(santorini_gods=11),
