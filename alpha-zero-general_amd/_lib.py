@@ -41,7 +41,7 @@ EXPORTS = [
     'azg_forest_root_stats', 'azg_forest_dump_tree', 'azg_forest_validate', 'azg_selfplay_start', 'azg_selfplay_start_ex', 'azg_selfplay_advance', 'azg_selfplay_active',
     'azg_selfplay_stats_get', 'azg_selfplay_drain_examples', 'azg_forest_last_kernel_ms', 'azg_forest_enable_timing', 'azg_forest_set_search_params', 'azg_nn_linear', 'azg_nn_linear_ws', 'azg_nn_dw_pool', 'azg_nn_v80_block', 'azg_nn_v80_forward', 'azg_nn_v80_forward_split', 'azg_nn_v80_forward_h2',
     'azg_nn_board_to_x', 'azg_nn_heads_out', 'azg_nn_dw_pool_l', 'azg_nn_board_to_x_ld', 'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
-    'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward',
+    'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62',
 ]
 
 
@@ -100,6 +100,8 @@ def lib():
             L.azg_forest_async_rounds_mb1d_h2.argtypes = [vp, i, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, vp]
         if hasattr(L, 'azg_forest_async_rounds_conv5_h2'):
             L.azg_forest_async_rounds_conv5_h2.argtypes = [vp, vp, vp, vp, vp, i, vp, C.c_float, i, i, i, i, i, vp]
+        if hasattr(L, 'azg_forest_async_rounds_sw62'):
+            L.azg_forest_async_rounds_sw62.argtypes = [vp, vp, vp, vp, vp, i, vp, i, i, i, i, i, vp]
         if hasattr(L, 'azg_forest_async_rounds_hashnet'):    # (test aid, include/azg_testaids.h)
             L.azg_forest_async_rounds_hashnet.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
         L.azg_forest_async_profile.argtypes = [vp, C.POINTER(C.c_double), i]

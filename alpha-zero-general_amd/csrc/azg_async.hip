@@ -22,8 +22,10 @@
 #include "nn_v80_h2.hip.h"
 #include "nn_conv5x5.hip.h"
 #include "nn_mb1d.hip.h"
+#include "nn_smallworld.hip.h"
 #include "game_santorini.hip.h"
 #include "game_azul.hip.h"
+#include "game_smallworld.hip.h"
 
 using namespace azg;
 

@@ -105,7 +105,9 @@ struct AsyncArgs {
     unsigned long long* wginfo;                // [n_sel + n_net][4]: where the workgroup ran (XCC | cu << 8 | se << 16 | sh << 24), role, calls, busy shader cycles
     int noise, rounds, n_sel, ring_bits, batch_wait, timeout_ticks;
     unsigned long long total_calls;            // != 0: the launch ends when the trees TOGETHER have had this many calls (whichever tree is fast
-};                                             // gets more of them: no tree waits for the slowest at the end of a launch); 0: `rounds` calls per tree
+                                               // gets more of them: no tree waits for the slowest at the end of a launch); 0: `rounds` calls per tree
+    Sw62NetW SW;                               // net V62 (Smallworld 2 - 4 players): nn_smallworld.hip.h (appended: the fields above keep their offsets)
+};
 __device__ __forceinline__ uint32_t where_am_i() {
     uint32_t xcc, hw;
     asm volatile("s_getreg_b32 %0, hwreg(20, 0, 4)" : "=s"(xcc));              // HW_REG_XCC_ID
@@ -619,11 +621,22 @@ struct NetHash {
         }
     }
 };
+template <int NPL>
+struct NetSw62 {                               // Smallworld 2 / 3 / 4 players: k_sw62_net<NPL>'s body, 4 / 3 / 2 leaves per forward
+    using G = SmallworldDev<NPL>;
+    static constexpr int BS = Sw62<NPL>::NS, LDS = (Sw62<NPL>::LDS_FLOATS * 4 + 255) / 256 * 256;
+    static_assert(G::A == Sw62<NPL>::A && G::S == Sw62<NPL>::N * 8, "the V62 geometry is the game's");
+    static __device__ __forceinline__ void run(uint8_t* lds, AsyncArgsC A, const int* sidx, unsigned long long* smask) {
+        sw62_net_body<NPL, true, AsyncLeaf<G>::STRIDE, AsyncLeaf<G>::MASK_OFF>((float*)lds, &A->SW, A->aleaf, (const uint8_t*)A->aleaf, A->F.T, A->pi, A->v, 0,
+                                                                                sidx, smask);
+    }
+};
 using NetSpl3 = NetMb1d<CfgSplendor3, SplendorDev<3>>;
 using NetSpl4 = NetMb1d<CfgSplendor4, SplendorDev<4>>;
 using NetAzul = NetMb1d<CfgAzul, AzulDev>;
 static_assert(NetV80::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetC5::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSpl4::LDS + ASYNC_DESC_BYTES <= 160 * 1024 &&
-              NetSpl3::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetAzul::LDS + ASYNC_DESC_BYTES <= 160 * 1024, "net LDS + batch descriptor");
+              NetSpl3::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetAzul::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSw62<2>::LDS + ASYNC_DESC_BYTES <= 160 * 1024 &&
+              NetSw62<3>::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSw62<4>::LDS + ASYNC_DESC_BYTES <= 160 * 1024, "net LDS + batch descriptor");
 static_assert(16 * 3 * 8 + H2_IND_MASK * 4 <= ASYNC_DESC_BYTES, "sixteen samples' three mask words behind the descriptor");
 
 template <class NET>
@@ -820,7 +833,8 @@ static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStrea
     HIPCHK(hipGetLastError());
     return 0;
 }
-// net_kind: 0 = Splendor 2 players (V80), 1 = Santorini no-gods (V89), 2 / 3 = Splendor 3 / 4 players, 4 = Azul (MobileNet-1d), 5 = Santorini with gods
+// net_kind: 0 = Splendor 2 players (V80), 1 = Santorini no-gods (V89), 2 / 3 = Splendor 3 / 4 players, 4 = Azul (MobileNet-1d), 5 = Santorini with gods,
+// 6 / 7 / 8 = Smallworld 2 / 3 / 4 players (V62)
 int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
 #ifdef AZG_ASYNC_ONLY_KIND      /* code-generation experiments: one game's kernel only */
     if (net_kind != AZG_ASYNC_ONLY_KIND) return -1;
@@ -835,6 +849,9 @@ int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_se
 #ifdef AZG_ASYNC_SANTORINI11
         case 5: return async_launch_select<azg::SantoriniDev<11>>(devbuf, n_sel, s);
 #endif
+        case 6: return async_launch_select<azg::SmallworldDev<2>>(devbuf, n_sel, s);
+        case 7: return async_launch_select<azg::SmallworldDev<3>>(devbuf, n_sel, s);
+        case 8: return async_launch_select<azg::SmallworldDev<4>>(devbuf, n_sel, s);
         default: return -1;
     }
 #endif
@@ -927,7 +944,8 @@ extern "C" int azg_forest_async_debug(azg_forest* f, unsigned long long* out /* 
 
 // One launch of the pipeline.  kind = which game's descent kernel (and, hash == 0, which net): 0 Splendor 2 players + V80 (w = 43 pointers,
 // descale = 16 host floats); 1 Santorini no-gods + V89 (w = 14 pointers, descale = 1 host float); 2 / 3 Splendor 3 / 4 players, 4 Azul
-// (MobileNet-1d: 43 pointers + 16 factors); 5 Santorini with gods (hash-net only so far).  hash != 0: the integer hash-net as the evaluator.
+// (MobileNet-1d: 43 pointers + 16 factors); 5 Santorini with gods (hash-net only so far); 6 / 7 / 8 Smallworld 2 / 3 / 4 players + V62 (w = 25
+// pointers, no descale).  hash != 0: the integer hash-net as the evaluator.
 // Recovery, first half: in front of the two persistent kernels, every tree that is still owed the evaluation of the leaf it queued in an
 // earlier launch (status ST_WAIT_NN, `evald` clear: that launch ended early) gets its leaf record -- still in the pipeline's leaf array --
 // back on the ring and is flagged `pending`: its descent workgroup starts it as "in the net".  Costs one tiny launch; in the common case
@@ -964,7 +982,10 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
                              int noise_stride, const void* const* w, const float* descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                              int shared_budget, void* stream) {
     const std::string me(who);
-    if (!f || !leaf_valid || !needs_eval || !pi || !v || (!hash && (!w || !descale))) return fail(me + ": null argument");
+    if (!f || !leaf_valid || !needs_eval || !pi || !v || (!hash && (!w || (kind < 6 && !descale)))) return fail(me + ": null argument");
+    if (!hash && kind >= 6)
+        for (int i = 0; i < SW_NW; i++)
+            if (!w[i]) return fail(me + ": null weight pointer");
     if (rounds < 0 || (rounds == 0 && shared_budget)) return 0;       // (per-tree budgets: rounds == 0 = only what earlier launches left over)
     if (rounds >= (1 << 24)) return fail(me + ": at most 2^24 - 1 rounds per launch");
     if (noise_stride != 0 && noise_stride != -2) return fail(me + ": noise_stride must be 0 or -2");
@@ -976,11 +997,14 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
     if ((kind == 2 || kind == 3) && (game != AZG_SPLENDOR || variant != kind + 1)) return fail(me + ": the geometry does not match the forest's game");
     if (kind == 4 && game != AZG_AZUL) return fail(me + ": the geometry does not match the forest's game");
     if (kind == 5 && (game != AZG_SANTORINI || variant != 11)) return fail(me + ": Santorini with gods only");
+    if (kind >= 6 && (game != AZG_SMALLWORLD || variant != kind - 4)) return fail(me + ": Smallworld only (the V62 geometry of nn_smallworld.hip.h)");
     static_assert(AsyncLeaf<SplendorDev<2>>::STRIDE == H2_AL_STRIDE && AsyncLeaf<SplendorDev<2>>::MASK_OFF == H2_AL_MASK, "leaf record layout shared with the net kernel");
     static_assert(AsyncLeaf<SantoriniDev<1>>::STRIDE == C5_AL_STRIDE && AsyncLeaf<SantoriniDev<1>>::MASK_OFF == C5_AL_MASK, "leaf record layout shared with the net kernel");
-    const int leaf_strides[6] = {H2_AL_STRIDE, C5_AL_STRIDE, AsyncLeaf<SplendorDev<3>>::STRIDE, AsyncLeaf<SplendorDev<4>>::STRIDE, AsyncLeaf<AzulDev>::STRIDE,
-                                 AsyncLeaf<SantoriniDev<11>>::STRIDE};
-    const int batch[6] = {NetV80::BS, NetC5::BS, NetSpl3::BS, NetSpl4::BS, NetAzul::BS, 16};
+    const int leaf_strides[9] = {H2_AL_STRIDE, C5_AL_STRIDE, AsyncLeaf<SplendorDev<3>>::STRIDE, AsyncLeaf<SplendorDev<4>>::STRIDE, AsyncLeaf<AzulDev>::STRIDE,
+                                 AsyncLeaf<SantoriniDev<11>>::STRIDE, AsyncLeaf<SmallworldDev<2>>::STRIDE, AsyncLeaf<SmallworldDev<3>>::STRIDE,
+                                 AsyncLeaf<SmallworldDev<4>>::STRIDE};
+    const int batch[9] = {NetV80::BS, NetC5::BS, NetSpl3::BS, NetSpl4::BS, NetAzul::BS, 16, NetSw62<2>::BS, NetSw62<3>::BS, NetSw62<4>::BS};
+    if (kind < 0 || kind >= 9) return fail(me + ": unknown pipeline kind");
     const int leaf_stride = leaf_strides[kind], bs = hash ? 16 : batch[kind];
     int device = 0;
     HIPCHK(hipGetDevice(&device));
@@ -994,7 +1018,9 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         HIPCHK(hipStreamCreateWithPriority(&b, hipStreamNonBlocking, hi));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
-        if (async_net_attr<NetV80>() || async_net_attr<NetC5>() || async_net_attr<NetSpl3>() || async_net_attr<NetSpl4>() || async_net_attr<NetAzul>()) return -1;
+        if (async_net_attr<NetV80>() || async_net_attr<NetC5>() || async_net_attr<NetSpl3>() || async_net_attr<NetSpl4>() || async_net_attr<NetAzul>() ||
+            async_net_attr<NetSw62<2>>() || async_net_attr<NetSw62<3>>() || async_net_attr<NetSw62<4>>())
+            return -1;
         D.net_stream = a; D.sel_stream = b; D.n_cu = prop.multiProcessorCount;
     }
     const int n_cu = D.n_cu;
@@ -1009,6 +1035,14 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         // 13 / 16 (200 + 56 -> 38.8 k, 208 + 48 40.1 k, 216 + 40 36.1 k); Azul (descent-heavy, forward 29 us per 16):
         // round 5 3 / 8 (96 + 160 -> 70.4 k; 112 + 144 68.6 k, 88 + 168 66.3 k), round 6 13 / 32 (96 + 160 69.9 k, 104 + 152 72.3 k).  The hash-net costs next to nothing: a sixteenth.
         n_net = hash ? (n_cu / 16 > 0 ? n_cu / 16 : 1) : kind == 0 ? n_cu * AZG_V80_NET_SHARE_256 / 256 : kind == 4 ? n_cu * 13 / 32 : (kind == 2 || kind == 3) ? n_cu * 13 / 16 : n_cu * 49 / 64;
+        // Smallworld + V62 (forward of 4 / 3 / 2 leaves 157 / 128 / 122 us, descent 36-48 us): 7 / 8 for the net, and never fewer
+        // descent workgroups than the 128 trees each can own need.  Measured at 200 simulations, 2 players x 1024 games: 240 + 16 -> 16.7 k plies/s
+        // (descent-bound: the waves 94 % busy, trees wait 24 us for one), 224 + 32 24.8 k, 208 + 48 25.4 k; 3 / 4 players x 512: 224 + 32 +4 / +6 %
+        // over 240 + 16
+        if (kind >= 6 && !hash) {
+            n_net = n_cu * 7 / 8;
+            if ((n_cu - n_net) * ASYNC_RS < T) { n_net = n_cu - (T + ASYNC_RS - 1) / ASYNC_RS; n_net = n_net < 1 ? 1 : n_net; }
+        }
         n_sel = n_cu - n_net;
     }
     if (n_sel > T) n_sel = T;
@@ -1060,6 +1094,10 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
     // would otherwise run its whole search inside ONE call: measured 4.1 ms launches of 48 rounds where the mean tree needs 3.4 ms)
     if (hash) {
     } else if (kind == 0) want.W = h2_weights(w, descale);
+    else if (kind >= 6) {                             // the 25 pointers of azg_nn_sw62_forward, in the order of Sw62NetW
+        static_assert(sizeof(Sw62NetW) == SW_NW * sizeof(const float*), "Sw62NetW is the 25-pointer table");
+        memcpy(&want.SW, w, sizeof(Sw62NetW));
+    }
     else if (kind >= 2) {                             // the 43-pointer table + 16 descale factors of azg_nn_mb1d_forward_h2
         const float* const* wf = (const float* const*)w;
         Mb1dNetW& N = want.MB;
@@ -1122,6 +1160,9 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
             case 2: rc = async_launch_net<NetHash<SplendorDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
             case 3: rc = async_launch_net<NetHash<SplendorDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
             case 4: rc = async_launch_net<NetHash<AzulDev>>(sl->devbuf, n_net, D.net_stream); break;
+            case 6: rc = async_launch_net<NetHash<SmallworldDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 7: rc = async_launch_net<NetHash<SmallworldDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 8: rc = async_launch_net<NetHash<SmallworldDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
 #ifdef AZG_ASYNC_SANTORINI11
             case 5: rc = async_launch_net<NetHash<SantoriniDev<11>>>(sl->devbuf, n_net, D.net_stream); break;
 #endif
@@ -1134,6 +1175,9 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
             case 2: rc = async_launch_net<NetSpl3>(sl->devbuf, n_net, D.net_stream); break;
             case 3: rc = async_launch_net<NetSpl4>(sl->devbuf, n_net, D.net_stream); break;
             case 4: rc = async_launch_net<NetAzul>(sl->devbuf, n_net, D.net_stream); break;
+            case 6: rc = async_launch_net<NetSw62<2>>(sl->devbuf, n_net, D.net_stream); break;
+            case 7: rc = async_launch_net<NetSw62<3>>(sl->devbuf, n_net, D.net_stream); break;
+            case 8: rc = async_launch_net<NetSw62<4>>(sl->devbuf, n_net, D.net_stream); break;
             default: return fail(me + ": no engine net for this game in the pipeline");
         }
     }
@@ -1174,6 +1218,19 @@ extern "C" int azg_forest_async_rounds_conv5_h2(azg_forest* f, uint8_t* leaf_val
                              n_net, n_sel, batch_wait_ticks, shared_budget, stream);
 }
 
+// include/azg.h: the pipeline for a Smallworld forest (2 / 3 / 4 players, read from the forest) with the V62 net (the 25 pointers of
+// azg_nn_sw62_forward)
+extern "C" int azg_forest_async_rounds_sw62(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
+                                            const float* const* w, int rounds, int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream) {
+    if (!f) return fail("azg_forest_async_rounds_sw62: null argument");
+    int game = 0, variant = 0;
+    double alpha = 0.0;
+    (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
+    if (game != AZG_SMALLWORLD || variant < 2 || variant > 4) return fail("azg_forest_async_rounds_sw62: Smallworld 2 - 4 players only (the V62 geometry of nn_smallworld.hip.h)");
+    return async_rounds_impl("azg_forest_async_rounds_sw62", variant + 4, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, (const void* const*)w, nullptr,
+                             rounds, n_net, n_sel, batch_wait_ticks, shared_budget, stream);
+}
+
 // include/azg_testaids.h: the pipeline with the integer hash-net as its evaluator, for every game that has a descent kernel here
 extern "C" int azg_forest_async_rounds_hashnet(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride, int rounds,
                                                int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream) {
@@ -1182,8 +1239,9 @@ extern "C" int azg_forest_async_rounds_hashnet(azg_forest* f, uint8_t* leaf_vali
     double alpha = 0.0;
     (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
     const int kind = game == AZG_SPLENDOR ? (variant == 2 ? 0 : variant == 3 ? 2 : variant == 4 ? 3 : -1)
-                     : game == AZG_SANTORINI ? (variant == 1 ? 1 : -1) : game == AZG_AZUL ? 4 : -1;
-    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for Splendor 2 - 4 players, Santorini without gods and Azul");
+                     : game == AZG_SANTORINI ? (variant == 1 ? 1 : -1) : game == AZG_AZUL ? 4
+                     : game == AZG_SMALLWORLD ? (variant >= 2 && variant <= 4 ? variant + 4 : -1) : -1;
+    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for Splendor 2 - 4 players, Santorini without gods, Azul and Smallworld 2 - 4 players");
     return async_rounds_impl("azg_forest_async_rounds_hashnet", kind, 1, f, leaf_valid, needs_eval, pi, v, noise_stride, nullptr, nullptr, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }

@@ -120,24 +120,52 @@ __device__ __forceinline__ void sw_store_row(float* __restrict__ r, int g, const
     for (int t = 0; t < 3; t++) *(float4*)(r + 16 * t + 4 * g) = make_float4(a[4 * t], a[4 * t + 1], a[4 * t + 2], a[4 * t + 3]);
 }
 
-template <int P>
-__global__ __launch_bounds__(SW_THREADS) void k_sw62_net(Sw62NetW W, const int8_t* __restrict__ boards, const uint8_t* __restrict__ valid,
-                                                       int B, float* __restrict__ pi, float* __restrict__ v) {
+// The forward of one workgroup (samples NS * wg ..) as a device function: the body of k_sw62_net and -- ASYNC -- of the asynchronous
+// pipeline's net kernel (azg_async.hip.h NetSw62): sample s of the workgroup is then tree sidx[s] (LDS; < 0 = no sample, computed on zero
+// tokens like a padding sample and not written), `boards` / `valid` are both the pipeline's leaf-record array (kernels.hip.h AsyncLeaf<G>:
+// int8 state [SP] = the [N][8] tokens + valid bit mask u64[AW] at AL_MASK, stride AL_STRIDE), read past the L1; the samples' masks are
+// fetched into `smask` (LDS u64 [NS][AW]); pi / v rows are written WRITE-THROUGH at the tree's index.  The weight table is read through
+// the CONSTANT address space (the kernel's own argument segment / the pipeline's argument block).
+typedef const Sw62NetW __attribute__((address_space(4))) * Sw62NetWC;
+#define W (*Wp)
+template <int P, bool ASYNC, int AL_STRIDE = 0, int AL_MASK = 0>
+__device__ __forceinline__ void sw62_net_body(float* lds, const Sw62NetWC Wp, const int8_t* __restrict__ boards, const uint8_t* __restrict__ valid,
+                                              int B, float* __restrict__ pi, float* __restrict__ v, const int wg, const int* sidx = nullptr,
+                                              unsigned long long* smask = nullptr) {
     using C = Sw62<P>;
-    __shared__ __attribute__((aligned(16))) float lds[C::LDS_FLOATS];
+    constexpr int AW = (C::A + 63) / 64;
     float* X = lds;                          // [ROWS][52]
     float* Q = X + C::ROWS * SW_XS;          // [ROWS][148]: q 0..47, k 48..95, v 96..143
     float* G = Q + C::ROWS * SW_QS;          // [NS][48]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
-    const int s0 = blockIdx.x * C::NS, ns = min(C::NS, B - s0);
+    int tid_ = threadIdx.x;
+    if (ASYNC) asm volatile("" : "+v"(tid_));            // (opaque inside the pipeline's persistent loop)
+    const int tid = tid_, lane = tid & 63, wave = tid >> 6, i16 = lane & 15, g = lane >> 4;
+    const int s0 = wg * C::NS, ns = ASYNC ? C::NS : min(C::NS, B - s0);
+    if constexpr (ASYNC) {
+        if (tid < C::NS * AW) {
+            const int b = sidx[tid / AW];
+            smask[tid] = b >= 0 ? __hip_atomic_load((const unsigned long long*)(valid + (size_t)b * AL_STRIDE + AL_MASK) + tid % AW, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT)
+                                : 0ull;
+        }
+    }
 
     // ---- stem: wave w < RT owns row tile w.  Padding rows and samples past B are computed on zero tokens (finite), stored as zero ----
     if (wave < C::RT) {
         const int row = wave * 16 + i16, s = row / C::NT, t = row - s * C::NT;
-        const bool live = s < ns && t < C::N;
         int c[8];
+        if constexpr (ASYNC) {               // (the token's 8 bytes in one agent-scope load: written write-through by a descent wave on another CU)
+            const int b = s < C::NS ? sidx[s] : -1;
+            const unsigned long long tok = b >= 0 && t < C::N ? __hip_atomic_load((const unsigned long long*)(boards + (size_t)b * AL_STRIDE) + t,
+                                                                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                                              : 0ull;
 #pragma unroll
-        for (int k = 0; k < 8; k++) c[k] = live ? (int)boards[((size_t)(s0 + s) * C::N + t) * 8 + k] : 0;
+            for (int k = 0; k < 8; k++) c[k] = (int)(int8_t)(tok >> (8 * k));
+        } else {
+            const bool live = s < ns && t < C::N;
+#pragma unroll
+            for (int k = 0; k < 8; k++) c[k] = live ? (int)boards[((size_t)(s0 + s) * C::N + t) * 8 + k] : 0;
+        }
         float f[21];
         f[0] = (float)c[0] / 10.f, f[1] = (float)c[3] / 10.f, f[2] = (float)c[4] / 10.f, f[3] = (float)c[5] / 10.f, f[4] = (float)c[6] / 10.f;
 #pragma unroll
@@ -289,19 +317,24 @@ __global__ __launch_bounds__(SW_THREADS) void k_sw62_net(Sw62NetW W, const int8_
             float a = W.bg[c];
             for (int d = 0; d < SW_D; d++) a = fmaf(gs[d], W.Wg[d * 16 + c], a);
             L[s * C::A + (c < 8 ? 4 * C::NA + c : 5 * C::NA + c)] = a;
-        } else if (s < ns) {
+        } else if (ASYNC ? sidx[s] >= 0 : s < ns) {
             float a = W.bv[c - 16];
             for (int d = 0; d < SW_D; d++) a = fmaf(gs[d], W.Wv[d * P + c - 16], a);
-            v[(size_t)(s0 + s) * P + c - 16] = tanhf(a);
+            if constexpr (ASYNC) __hip_atomic_store((uint32_t*)v + (size_t)sidx[s] * P + c - 16, __float_as_uint(tanhf(a)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else v[(size_t)(s0 + s) * P + c - 16] = tanhf(a);
         }
     }
     __syncthreads();
-    if (wave < ns) {                    // masked softmax of sample `wave` (invalid -> -1e8, as the reference)
+    if (wave < ns && (!ASYNC || sidx[wave] >= 0)) {          // masked softmax of sample `wave` (invalid -> -1e8, as the reference)
+        const int b = ASYNC ? sidx[wave] : s0 + wave;
         float* lg = L + wave * C::A;
-        const uint8_t* va = valid + (size_t)(s0 + wave) * C::A;
+        const uint8_t* va = valid + (size_t)b * C::A;
         float mx = -3.0e38f;
         for (int a = lane; a < C::A; a += 64) {
-            const float x = va[a] ? lg[a] : -1e8f;
+            bool ok;
+            if constexpr (ASYNC) ok = (smask[wave * AW + (a >> 6)] >> lane) & 1ull;
+            else ok = va[a];
+            const float x = ok ? lg[a] : -1e8f;
             lg[a] = x;
             mx = fmaxf(mx, x);
         }
@@ -313,9 +346,22 @@ __global__ __launch_bounds__(SW_THREADS) void k_sw62_net(Sw62NetW W, const int8_
             sum += e;
         }
         sum = nn_wave_sum(sum);
-        float* po = pi + (size_t)(s0 + wave) * C::A;
-        for (int a = lane; a < C::A; a += 64) po[a] = lg[a] / sum;
+        float* po = pi + (size_t)b * C::A;
+        for (int a = lane; a < C::A; a += 64) {
+            if constexpr (ASYNC) __hip_atomic_store((uint32_t*)po + a, __float_as_uint(lg[a] / sum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else po[a] = lg[a] / sum;
+        }
     }
+}
+#undef W
+
+template <int P>
+__global__ __launch_bounds__(SW_THREADS) void k_sw62_net(Sw62NetW W /* first argument: offset 0 of the kernel argument segment, read through it */,
+                                                       const int8_t* __restrict__ boards, const uint8_t* __restrict__ valid, int B,
+                                                       float* __restrict__ pi, float* __restrict__ v) {
+    __shared__ __attribute__((aligned(16))) float lds[Sw62<P>::LDS_FLOATS];
+    (void)W;
+    sw62_net_body<P, false>(lds, (Sw62NetWC)__builtin_amdgcn_kernarg_segment_ptr(), boards, valid, B, pi, v, (int)blockIdx.x);
 }
 
 }  // namespace azg

@@ -135,6 +135,13 @@ class Forest:
                                                         -2 if device_noise else 0, net.fused_ptrs_h2, net.descale_h2, int(rounds), int(n_net), int(n_sel),
                                                         int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
             return
+        if self.cfg.game == _lib.SMALLWORLD:           # the V62 transformer (SmallworldV62Hip: the 25 pointers of azg_nn_sw62_forward)
+            if type(net).__name__ != 'SmallworldV62Hip':
+                raise ValueError('the Smallworld pipeline evaluates SmallworldV62Hip (the engine kernel), not %s' % type(net).__name__)
+            check(lib().azg_forest_async_rounds_sw62(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
+                                                     -2 if device_noise else 0, net.ptrs, int(rounds), int(n_net), int(n_sel),
+                                                     int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
+            return
         if self.cfg.game == _lib.SANTORINI:            # the V89 net (SantoriniV89Hip: 14 pointers + the trunk's descale)
             check(lib().azg_forest_async_rounds_conv5_h2(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
                                                          -2 if device_noise else 0, net.ptrs, float(net.descale), int(rounds), int(n_net), int(n_sel),

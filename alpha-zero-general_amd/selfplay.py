@@ -140,11 +140,17 @@ class SelfPlayEngine:
         can_hash = (self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_hashnet') and all(getattr(n, 'async_hashnet', False) for n in nets) and
                     ((gid == _lib.SPLENDOR and var in (0, 2, 3, 4)) or (gid == _lib.SANTORINI and var == 1) or gid == _lib.AZUL))
         any_pipe = can or can_c5 or can_mb or can_hash
+        # ... and, OPT-IN only (async_pipe=True; the default stays the two-kernel rounds until the numbers decide otherwise), for
+        # Smallworld 2 - 4 players + the V62 transformer on its one-launch kernel (SmallworldV62Hip) with static output buffers, or the tests' hash-net
+        sw = gid == _lib.SMALLWORLD and var in (2, 3, 4) and self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_sw62')
+        can_sw = sw and (all(type(n).__name__ == 'SmallworldV62Hip' and torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game)
+                             for n in nets) or all(getattr(n, 'async_hashnet', False) for n in nets))
         if async_pipe is None:
             async_pipe = any_pipe and groups == 1 and not percu and os.environ.get('AZG_ASYNC', '1') == '1'
-        elif async_pipe and not (any_pipe and groups == 1):
-            raise ValueError('async_pipe=True needs Splendor 2 players + SplendorV80Hip(h2=True), Santorini no-gods + SantoriniV89Hip(h2=True) or Splendor 3 / 4 '
-                             'players / Azul + MobileNet1dHip(h2=True) evaluators with max_batch == n_games (or the tests\' hash-net), groups == 1')
+        elif async_pipe and not ((any_pipe or can_sw) and groups == 1):
+            raise ValueError('async_pipe=True needs Splendor 2 players + SplendorV80Hip(h2=True), Santorini no-gods + SantoriniV89Hip(h2=True), Splendor 3 / 4 '
+                             'players / Azul + MobileNet1dHip(h2=True) or Smallworld 2 - 4 players + SmallworldV62Hip evaluators with max_batch == n_games '
+                             '(or the tests\' hash-net), groups == 1')
         self.async_pipe = bool(async_pipe)
         self.adaptive = False
         if work_budget is None:

@@ -216,6 +216,14 @@ int azg_forest_async_rounds_conv5_h2(azg_forest* f, uint8_t* leaf_valid_dev, uin
 int azg_forest_async_rounds_mb1d_h2(azg_forest* f, int geometry, uint8_t* leaf_valid_dev, uint8_t* needs_eval_dev, float* pi_dev, float* v_dev,
                                     int noise_stride, const void* const* w, const float* descale_host, int rounds, int n_net, int n_sel,
                                     int batch_wait_ticks, int shared_budget, void* stream);
+/* ... and for Smallworld 2 / 3 / 4 players (the player count is the forest's) with the V62 transformer: the lock ring of game threads
+   around one inference server (Coach.py:117-144, GenericNNetWrapper.py:122-157) with SmallworldNNet.py nn_version 62 as the net.
+   w = the 25 device pointers of azg_nn_sw62_forward (no descale), 4 / 3 / 2 leaves per forward (the samples of one k_sw62_net workgroup);
+   default split 7 / 8 of the CUs for the net, fewer when the trees need more descent workgroups (at most 128 trees each).  Per-tree results
+   are identical bit for bit to `rounds` x (azg_forest_select_fused -> azg_selfplay_advance -> azg_nn_sw62_forward) with shared_budget == 0.
+   A null argument or a forest of another game: an error, nothing is launched.  Everything else as above. */
+int azg_forest_async_rounds_sw62(azg_forest* f, uint8_t* leaf_valid_dev, uint8_t* needs_eval_dev, float* pi_dev, float* v_dev, int noise_stride,
+                                 const float* const* w, int rounds, int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream);
 /* measurement: counters of the pipeline since the last reset (ticks = 10 ns of the 100 MHz wall clock read inside the kernels):
    out[0] descents (select_tree calls), [1] ticks inside them, [2] ticks descent waves spent looking for a ready tree, [3] net batches,
    [4] leaves in them, [5] ticks inside the forward, [6] ticks net workgroups waited for leaves, [7] sum over leaves of (claimed by a net

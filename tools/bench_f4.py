@@ -2,6 +2,7 @@
 self-play on the engine with the integer hash-net of SURVEY Appendix C.3 as the leaf evaluator (these games have no engine net; the
 figure is the env step + tree side of the plugin, `nnet.TorchModuleEvaluator` adds the user's PyTorch-ROCm module on top).
     python tools/bench_f4.py [--games 1024 --sims 200 --plies 12]
+    python tools/bench_f4.py --net engine --pipe --only smallworld    (the V62 net on the asynchronous tree pipeline, csrc/azg_async.hip.h)
 One JSON line per game: plies/s, simulations/s, ms per round, levels per simulation, valid actions per level, engine errors,
 structural validation of the forest afterwards."""
 import argparse
@@ -67,10 +68,15 @@ def main():
     ap.add_argument('--sims', type=int, default=200)
     ap.add_argument('--plies', type=int, default=40, help='timed ply waves (one wave = `sims` lock-step rounds)')
     ap.add_argument('--only', default=None)
+    ap.add_argument('--pipe', action='store_true', help='with --net engine: run the Smallworld rows on the asynchronous tree pipeline (async_pipe=True; '
+                                                           'AZG_ASYNC_NNET / AZG_ASYNC_NSEL set the CU split) and report its profile; other rows are skipped')
     ap.add_argument('--cyc', action='store_true', help='cycle breakdown of k_select per tree and launch (a library built with AZG_DEFINES=AZG_CYC_COUNTERS)')
     a = ap.parse_args()
     for name, make, scale, capf in GAMES:
         if a.only and a.only != name:
+            continue
+        pipe = a.pipe and a.net == 'engine'
+        if pipe and not name.startswith('smallworld'):
             continue
         g = make()
         T = max(64, int(a.games * scale))
@@ -112,10 +118,12 @@ def main():
             net.bind_outputs(T, g.A, g.P, g.device)          # fixed output buffers: the engine's expansion reads them in place (no copy kernels per round)
         else:
             net = HashNetTorch(g.P)
-        eng = SelfPlayEngine(g, net, args, n_games=T, node_capacity=max(2048, capf * a.sims), max_examples=T * 256)
+        eng = SelfPlayEngine(g, net, args, n_games=T, node_capacity=max(2048, capf * a.sims), max_examples=T * 256, **(dict(async_pipe=True) if pipe else {}))
         eng.start()
         eng.run(2 * a.sims)                                    # warm-up: two ply waves (also captures the HIP graph)
         torch.cuda.synchronize()
+        if pipe:
+            eng.forest.async_profile(reset=True)
         s0 = eng.stats()
         t0 = time.perf_counter()
         eng.run(a.plies * a.sims)
@@ -123,10 +131,12 @@ def main():
         dt = time.perf_counter() - t0
         s1 = eng.stats()
         sims, plies = s1['sims'] - s0['sims'], s1['plies'] - s0['plies']
+        prof = eng.forest.async_profile(reset=True) if pipe else None
         bad = sum(grp.f.validate(verbose=False) for grp in eng.groups)
+        evaluator = a.net + ('+pipe' if pipe else '')
         if a.md:
             print('| %s | %d | %d | %d | %d | %s | %.0f | %.2f | %.3f | %.2f | %.1f | %d | %d | %.1f |' % (
-                name, g.P, g.S, g.A, T, a.net, plies / dt, sims / dt / 1e6, dt / (a.plies * a.sims) * 1e3, (s1['levels'] - s0['levels']) / max(sims, 1),
+                name, g.P, g.S, g.A, T, evaluator, plies / dt, sims / dt / 1e6, dt / (a.plies * a.sims) * 1e3, (s1['levels'] - s0['levels']) / max(sims, 1),
                 (s1['sum_valid_visited'] - s0['sum_valid_visited']) / max(s1['levels'] - s0['levels'], 1), s1['errors'], bad, eng.device_bytes / 1e9), flush=True)
         else:
             print(json.dumps(dict(game=name, players=g.P, state_bytes=g.S, actions=g.A, games=T, sims_per_move=a.sims, plies_per_s=plies / dt,
@@ -134,7 +144,10 @@ def main():
                                   levels_per_sim=(s1['levels'] - s0['levels']) / max(sims, 1),
                                   valid_per_level=(s1['sum_valid_visited'] - s0['sum_valid_visited']) / max(s1['levels'] - s0['levels'], 1),
                                   games_finished=s1['games'], errors=s1['errors'], validate_violations=bad,
-                                  forest_gb=eng.device_bytes / 1e9, evaluator=a.net)), flush=True)
+                                  forest_gb=eng.device_bytes / 1e9, evaluator=evaluator,
+                                  **({} if prof is None else dict(pipeline={k: prof[k] for k in ('n_sel', 'n_net', 'descent_us', 'forward_us', 'leaves_per_batch',
+                                                                                                   'leaf_wait_us', 'ready_wait_us', 'select_wave_busy', 'net_wg_busy',
+                                                                                                   'launches', 'timeouts')})))), flush=True)
         if a.cyc and 'cyc_seg' in s1:
             n = a.plies * a.sims * T
             seg = [s1['cyc_seg'][k] - s0['cyc_seg'][k] for k in range(4)]
