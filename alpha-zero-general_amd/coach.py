@@ -26,7 +26,7 @@ import torch
 
 from . import formats
 from .arena import BatchedArena
-from .nnet_wrapper import NNetWrapper
+from .nnet_wrapper import NNetWrapper, is_engine_module
 from .selfplay import SelfPlayEngine
 
 
@@ -60,10 +60,7 @@ class Coach:
         than one rank; False = single process; True = go through the collectives even at world size 1"""
         self.game, self.args, self.log = game, args, log
         if not hasattr(nnet, 'save_checkpoint'):                     # a bare torch module: give it the NeuralNet surface
-            from . import train as _train
-            engine_module = isinstance(nnet, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
-                                                   _train.AbaloneV21Module, _train.SmallworldV62Module, _train.AkropolisV31Module,
-                                                   _train.MinivillesV82Module, _train.TLPV83Module, _train.BotanikV10Module))
+            engine_module = is_engine_module(nnet)
             w = NNetWrapper(game, dict(nn_version=getattr(nnet, 'version', -1), learn_rate=_get(args, 'learn_rate', 3e-3),
                                        batch_size=_get(args, 'batch_size', 512), epochs=_get(args, 'epochs', 2),
                                        q_weight=_get(args, 'q_weight', 0.5), dropout=_get(args, 'dropout', 0.0)),

@@ -7,6 +7,9 @@ SplendorV80 re-expresses the reference's nn_version == 80 network (splendor/Sple
 blocks :148-202) in plain torch -- no torchvision -- in channels-last layout [B, 7, C] so every token-axis Linear is a
 plain GEMM, with BatchNorm folded into the GEMM weights (eval mode) and the Flatten permutation folded into the first
 head Linear.  It loads the reference's state_dict key names unchanged (checkpoint compatibility)."""
+import copy
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -17,6 +20,80 @@ def _fold_bn(sd, prefix, eps=1e-5):
     m, v = sd[prefix + '.running_mean'], sd[prefix + '.running_var']
     s = g / torch.sqrt(v + eps)
     return s, b - m * s
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class _TorchNet:
+    """NeuralNet-style entry points of the plain-torch nets: a subclass has __init__(state_dict, ..., device=...), device and
+    forward(boards, valids bool) -> (pi, v)."""
+
+    @classmethod
+    def from_npz(cls, path, **kw):
+        z = np.load(path)
+        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
+
+    # NeuralNet.predict-compatible entry points
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
+        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+class _EngineNet:
+    """An engine evaluator: a net's weights packed for one of the engine's one-launch forward kernels, with static pi [maxB, A] /
+    v [maxB, P] output buffers (the engine's rounds are captured into HIP graphs with them).  A subclass sets _lib, device, A, P,
+    S (the board width in bytes) and ptrs (the weight pointer table), and either names the C entry point in _FN with the integers
+    it takes before B in _ints(), or overrides _launch (boards, valids: device pointers)."""
+    _FN = None
+
+    def _ints(self):
+        raise NotImplementedError
+
+    def _alloc(self, B):
+        self.maxB = B
+        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
+        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
+
+    def clone_buffers(self):
+        """a second evaluator sharing the (read-only) weights but with its own activation buffers (concurrent streams)"""
+        other = copy.copy(self)
+        other._alloc(self.maxB)
+        return other
+
+    @staticmethod
+    def _stream():
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    @torch.no_grad()
+    def forward(self, boards, valids):
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        boards = boards.reshape(B, -1)
+        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == self.S
+        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+        assert valids.shape == (B, self.A) and valids.is_cuda
+        self._launch(_ptr(boards), _ptr(valids), B, self._stream())
+        return self.pi[:B], self.v[:B]
+
+    def _launch(self, boards, valids, B, stream):
+        self._lib.check(getattr(self._lib.lib(), self._FN)(boards, valids, self.ptrs, *self._ints(), B, _ptr(self.pi), _ptr(self.v), stream))
+
+    def predict_batch(self, boards, valids):
+        return self.forward(boards, valids)
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.forward(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()
 
 
 class _Block:
@@ -55,7 +132,7 @@ class _Block:
         return out + x if self.Wp.shape[1] == x.shape[-1] else out             # use_res_connect: in == out channels
 
 
-class SplendorV80:
+class SplendorV80(_TorchNet):
     """forward(board int8/float [B,56,7], valid bool [B,81]) -> (pi probabilities f32 [B,81], v f32 [B,P])."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
@@ -87,11 +164,6 @@ class SplendorV80:
             for name in blk.tensors():
                 setattr(blk, name, getattr(blk, name).to(self.device, dtype))
         return self
-
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
 
     @classmethod
     def random_init(cls, num_players=2, seed=0, **kw):
@@ -140,21 +212,12 @@ class SplendorV80:
         pi = torch.softmax(logits, dim=1)              # exp(log_softmax) of GenericNNetWrapper.py:107,119
         return pi.contiguous(), v.contiguous()
 
-    # NeuralNet.predict-compatible entry points
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class SplendorV80Hip(SplendorV80):
+class SplendorV80Hip(SplendorV80, _EngineNet):
     """Same network, same weights, evaluated by the engine's own gfx950 kernels (azg_nn_* in include/azg.h) instead of
     ~70 torch ops: 9 skinny fp32 MFMA GEMMs (k_linear, with bias / activation / residual / SE-scale fused), 3
-    depthwise+BN+act+pool kernels, 3 SE kernels, one layout kernel and one softmax/value kernel per leaf batch."""
+    depthwise+BN+act+pool kernels, 3 SE kernels, one layout kernel and one softmax/value kernel per leaf batch.  Its own
+    activation buffers and forward; predict takes bool valids (SplendorV80's)."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', max_batch=4096, split=True, h2=None):
         """h2 (default for the 2-player geometry): the one-launch forward on fp16 hi+lo split operands with token-major tiles
@@ -192,17 +255,6 @@ class SplendorV80Hip(SplendorV80):
         self.pi = torch.empty((B, self.A), dtype=f, device=d)
         self.v = torch.empty((B, self.P), dtype=f, device=d)
 
-    def clone_buffers(self):
-        """a second evaluator sharing the (read-only) weights but with its own activation buffers (concurrent streams)"""
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    def _stream(self):
-        import ctypes as C
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     @staticmethod
     def _pad_w(W):
         """[K][N] -> zero-padded [Kp][NP], Kp multiple of 16, NP/16 in {1,4,6,11} (k_linear's LDS / fragment layout)"""
@@ -227,7 +279,6 @@ class SplendorV80Hip(SplendorV80):
     def _net_ptrs(self):
         """device pointer table of azg_nn_v80_forward (include/azg.h): first layer, 3 blocks, head Linears re-indexed to the
         in-LDS flatten k = l*60 + c"""
-        import ctypes as C
         assert (self.trunk.use_hs, self.trunk.setype) == (False, 'avg')
         assert (self.head_pi.use_hs, self.head_pi.setype) == (True, 'max') and (self.head_v.use_hs, self.head_v.setype) == (True, 'max')
         assert self.C == 56 and self.A == 81
@@ -270,7 +321,6 @@ class SplendorV80Hip(SplendorV80):
     def _h2_ptrs(self):
         """pointer table + descale factors of azg_nn_v80_forward_h2 (include/azg.h): every matrix zero padded to K % 32 == 0,
         N % 16 == 0, scaled by 2^k (max |w| * 2^k in (2^11, 2^12]) and split into f16 hi / lo fragments"""
-        import ctypes as C
         import math
         d, f = self.device, torch.float32
 
@@ -316,7 +366,6 @@ class SplendorV80Hip(SplendorV80):
         self.descale_h2 = (C.c_float * 16)(*desc)
 
     def _linear(self, A, lda, Wp, bias, out, ldc, M, K, N, act=0, R=None, ldr=0, rowscale=None, rpg=0, ksplit=0):
-        import ctypes as C
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         if self.weight_stationary:
             bp = None
@@ -351,8 +400,6 @@ class SplendorV80Hip(SplendorV80):
         return Wp.view(Kp // 16, 4, 4, NP // 16, 16).permute(3, 0, 1, 4, 2).contiguous().view(-1)
 
     def _block_ptrs(self, blk):
-        import ctypes as C
-
         def pad1(v, n):
             out = torch.zeros(n, dtype=torch.float32, device=v.device)
             out[:v.numel()] = v
@@ -365,7 +412,6 @@ class SplendorV80Hip(SplendorV80):
         blk.ptrs = (C.c_void_p * 11)(*[t.data_ptr() for t in blk._keep])
 
     def _block(self, blk, xin, xout, B):
-        import ctypes as C
         L = self._lib.lib()
         if self.fused_blocks:
             self._lib.check(L.azg_nn_v80_block(C.c_void_p(xin.data_ptr()), C.c_void_p(xout.data_ptr()), blk.ptrs, B,
@@ -384,7 +430,6 @@ class SplendorV80Hip(SplendorV80):
 
     @torch.no_grad()
     def forward(self, boards, valids):
-        import ctypes as C
         B = boards.shape[0]
         if B > self.maxB:
             self._alloc(B)
@@ -501,7 +546,7 @@ MB1D_GEOMETRY = {(7, 56): 0, (7, 71): 1, (7, 88): 2, (6, 23): 3, (2, 58): 4, (15
                  (2, 78): 6, (2, 98): 7, (15, 73): 8, (15, 91): 9}
 
 
-class MobileNet1dHip:
+class MobileNet1dHip(_EngineNet):
     """The MobileNetV3-1d policy/value nets of any geometry (Splendor V80 for 2-4 players: C = 32 + 10n + n^2 channels x 7
     tokens; Azul V84: 23 channels x 6 tokens, AzulNNet.py:91-113) evaluated by the engine's gfx950 kernels instead of ~65
     torch ops per leaf batch: azg_nn_board_to_x_ld, then per InvertedResidual1d block (SplendorNNet.py:189-202) expand GEMM
@@ -573,7 +618,6 @@ class MobileNet1dHip:
     def _pack_fused(self, padw, padv, r16):
         """the 43 weight pointers of azg_nn_mb1d_forward: matrices zero-padded to multiples of 16 and stored in MFMA
         fragment order, vectors zero-padded to multiples of 16"""
-        import ctypes as C
         base, L, frag = self.base, self.L, SplendorV80Hip._frag
         fw = lambda W: frag(padw(W, r16(W.shape[0]), r16(W.shape[1])))  # noqa: E731
         keep = [fw(base.W0), padv(base.b0, r16(self.C))]
@@ -638,14 +682,7 @@ class MobileNet1dHip:
         self.pi = torch.empty((B, self.A), dtype=f, device=d)
         self.v = torch.empty((B, self.P), dtype=f, device=d)
 
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
     def _lin(self, A, lda, Wp, bias_p, out, ldc, M, K, N, act=0, R=None, ldr=0, rowscale=None, rpg=0, ksplit=False):
-        import ctypes as C
         p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
         L = self._lib.lib()
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -658,7 +695,6 @@ class MobileNet1dHip:
                                             M, K, N, act, 1 if ksplit else 0, st))
 
     def _block(self, g, xin, xout, B):
-        import ctypes as C
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
         M, Ep = B * self.L, g['Ep']
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -672,7 +708,6 @@ class MobileNet1dHip:
 
     @torch.no_grad()
     def forward(self, boards, valids):
-        import ctypes as C
         B = boards.shape[0]
         if B > self.maxB:
             self._alloc(B)
@@ -705,17 +740,8 @@ class MobileNet1dHip:
                                             p(self.pi), p(self.v), B, self.A, self.P, st))
         return self.pi[:B], self.v[:B]
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class SantoriniV89:
+class SantoriniV89(_TorchNet):
     """santorini/SantoriniNNet.py nn_version 88/89 (:194-219,273-281; SimpleResBlock :71-84, SimpleHead :17-40): the 2
     spatial planes (workers, levels) of the (5,5,3) board -> conv3x3(2->64)+BN+ReLU -> 5 residual blocks -> 1x1-conv heads.
     BatchNorm folded into the convolutions (eval mode); plain torch ops (MIOpen / hipBLASLt)."""
@@ -749,11 +775,6 @@ class SantoriniV89:
         self.fc_pi, self.fc_v1, self.fc_v2 = mv(self.fc_pi), mv(self.fc_v1), mv(self.fc_v2)
         return self
 
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
-
     @torch.no_grad()
     def forward(self, boards, valids):
         B = boards.shape[0]
@@ -769,25 +790,16 @@ class SantoriniV89:
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class SantoriniV89Hip:
+class SantoriniV89Hip(_EngineNet):
     """SantoriniV89 (no-gods geometry: 5 residual blocks, A = 162) evaluated by the engine's one-launch implicit-GEMM kernel
     (azg_nn_conv5_forward, csrc/nn_conv5x5.hip.h) instead of 11 MIOpen convolutions + glue ops.  Wraps a SantoriniV89."""
+    S = 75
 
     def __init__(self, base, max_batch=4096, split=True, h2=True):
         """h2 (default): the trunk convolutions on f16 x 2 split-precision operands (azg_nn_conv5_forward_h2: three f16 MFMAs per
         product, 22-bit operands, same 1e-5 contract).  Otherwise split: bf16 x 3 (azg_nn_conv5_forward_split, six MFMAs per
         product); False = the f32-MFMA kernel"""
-        import ctypes as C
         import math
         from . import _lib
         self._lib, self.base, self.device, self.split, self.h2 = _lib, base, base.device, bool(split), bool(h2)
@@ -834,44 +846,14 @@ class SantoriniV89Hip:
         self.ptrs = (C.c_void_p * 14)(*[t.data_ptr() for t in keep])
         self._alloc(max_batch)
 
-    def _alloc(self, B):
-        self.maxB = B
-        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
-        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 75
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+    def _launch(self, boards, valids, B, stream):
+        L = self._lib.lib()
         if self.h2:
-            self._lib.check(self._lib.lib().azg_nn_conv5_forward_h2(p(boards), p(valids), self.ptrs, self.descale, 5, self.A, self.P, B, p(self.pi),
-                                                                    p(self.v), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            return self.pi[:B], self.v[:B]
-        fwd = self._lib.lib().azg_nn_conv5_forward_split if self.split else self._lib.lib().azg_nn_conv5_forward
-        self._lib.check(fwd(p(boards), p(valids), self.ptrs, 5, self.A, self.P, B, p(self.pi), p(self.v),
-                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
-
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
-
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+            self._lib.check(L.azg_nn_conv5_forward_h2(boards, valids, self.ptrs, self.descale, 5, self.A, self.P, B, _ptr(self.pi), _ptr(self.v),
+                                                      stream))
+            return
+        fwd = L.azg_nn_conv5_forward_split if self.split else L.azg_nn_conv5_forward
+        self._lib.check(fwd(boards, valids, self.ptrs, 5, self.A, self.P, B, _ptr(self.pi), _ptr(self.v), stream))
 
 
 class SantoriniV78(SantoriniV89):
@@ -938,7 +920,6 @@ class SantoriniV78Hip(SantoriniV89Hip):
         """h2 (default): the 1x1 convolutions of the trunk and the depthwise pass on f16 x 2 split-precision operands
         (azg_nn_s78_forward_h2: three MFMAs per product).  Otherwise split: bf16 x 3 (azg_nn_s78_forward_split, 8 samples per
         workgroup, the expanded tile in thirds); False = the f32-MFMA kernel (4 samples per workgroup)"""
-        import ctypes as C
         import math
         from . import _lib
         self._lib, self.base, self.device, self.split, self.h2 = _lib, base, base.device, bool(split) or bool(h2), bool(h2)
@@ -1003,28 +984,17 @@ class SantoriniV78Hip(SantoriniV89Hip):
         self.ptrs = (C.c_void_p * 19)(*[t.data_ptr() for t in keep])
         self._alloc(max_batch)
 
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 75
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
+    def _launch(self, boards, valids, B, stream):
+        L = self._lib.lib()
         if self.h2:
-            self._lib.check(self._lib.lib().azg_nn_s78_forward_h2(p(boards), p(valids), self.ptrs, self.ds_e, self.ds_p, 10, self.A, self.P, B,
-                                                                  p(self.pi), p(self.v), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            return self.pi[:B], self.v[:B]
-        fwd = self._lib.lib().azg_nn_s78_forward_split if self.split else self._lib.lib().azg_nn_s78_forward
-        self._lib.check(fwd(p(boards), p(valids), self.ptrs, 10, self.A, self.P, B, p(self.pi), p(self.v),
-                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
+            self._lib.check(L.azg_nn_s78_forward_h2(boards, valids, self.ptrs, self.ds_e, self.ds_p, 10, self.A, self.P, B, _ptr(self.pi),
+                                                    _ptr(self.v), stream))
+            return
+        fwd = L.azg_nn_s78_forward_split if self.split else L.azg_nn_s78_forward
+        self._lib.check(fwd(boards, valids, self.ptrs, 10, self.A, self.P, B, _ptr(self.pi), _ptr(self.v), stream))
 
 
-
-class AbaloneV21:
+class AbaloneV21(_TorchNet):
     """abalone/AbaloneNNet.py nn_version 21 (:120-160, forward :173-201) -- the net of pretrained_BelgianDaisy.pt: the 3 spatial
     planes (marbles of each player, hex mask) of the (9, 9, 4) board -> conv3x3(3->24)+BN+ReLU -> 4 torchvision InvertedResidual
     blocks (1x1 expand 24->48 + BN + ReLU, depthwise 3x3 + BN + ReLU, 1x1 project + BN, residual; no SE) -> policy 1x1 conv
@@ -1059,11 +1029,6 @@ class AbaloneV21:
         self.fc_v1, self.fc_v2 = mv(self.fc_v1), mv(self.fc_v2)
         return self
 
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
-
     @torch.no_grad()
     def forward(self, boards, valids):
         B = boards.shape[0]
@@ -1080,24 +1045,15 @@ class AbaloneV21:
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class AbaloneV21Hip:
+class AbaloneV21Hip(_EngineNet):
     """AbaloneV21 (4 InvertedResidual blocks on the 9 x 9 grid, A = 3402) evaluated by the engine's one-launch kernel
     (azg_nn_aba21_forward, csrc/nn_abalone.hip.h: f32 MFMA GEMMs for the convolutions, the depthwise 3x3 on the vector ALUs, heads
     and masked softmax in the same launch) instead of ~20 MIOpen / hipBLASLt launches.  Wraps an AbaloneV21; static pi / v buffers
     (HIP-graph capture of the engine's rounds)."""
+    _FN, S = 'azg_nn_aba21_forward', 324
 
     def __init__(self, base, max_batch=4096):
-        import ctypes as C
         from . import _lib
         self._lib, self.base, self.device = _lib, base, base.device
         self.P, self.A = base.P, base.A
@@ -1129,43 +1085,11 @@ class AbaloneV21Hip:
         assert tuple(base.fc_v1[0].shape) == (340, 64) and tuple(base.meta[0].shape) == (6, 16)
         return keep
 
-    def _alloc(self, B):
-        self.maxB = B
-        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
-        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 324
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
-        assert valids.shape == (B, self.A) and valids.is_cuda
-        self._lib.check(self._lib.lib().azg_nn_aba21_forward(p(boards), p(valids), self.ptrs, 4, self.A, self.P, B, p(self.pi), p(self.v),
-                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
-
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
-
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+    def _ints(self):
+        return (4, self.A, self.P)
 
 
-class SmallworldV62:
+class SmallworldV62(_TorchNet):
     """smallworld/SmallworldNNet.py nn_version 62 (:246-254, stem :86-137, heads :139-180, forward :268-294) -- the net of all three shipped
     checkpoints (pretrained_{2,3,4}pl.pt): InputStem over the (N, 8) tokens -> 48, three post-norm TransformerEncoderLayers (3 heads of 16,
     feed-forward 192, ReLU, LayerNorm eps 1e-5, no mask), ActionSlicerHead (local 48 -> 5 on the nA area tokens, mean of the other tokens
@@ -1214,11 +1138,6 @@ class SmallworldV62:
         self.shifts = torch.arange(8, device=self.device)
         return self
 
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
-
     @torch.no_grad()
     def forward(self, boards, valids):
         B = boards.shape[0]
@@ -1247,27 +1166,18 @@ class SmallworldV62:
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class SmallworldV62Hip:
+class SmallworldV62Hip(_EngineNet):
     """SmallworldV62 (3 transformer layers, P = 2 / 3 / 4) evaluated by the engine's one-launch kernel (azg_nn_sw62_forward,
     csrc/nn_smallworld.hip.h: f32 MFMA for the per-token GEMMs and the two attention products, stem / softmax / LayerNorm / heads on
     the vector ALUs, masked softmax in the same launch) instead of ~40 torch launches.  Wraps a SmallworldV62; static pi / v buffers
     (HIP-graph capture of the engine's rounds)."""
+    _FN = 'azg_nn_sw62_forward'
 
     def __init__(self, base, max_batch=4096):
-        import ctypes as C
         from . import _lib
         self._lib, self.base, self.device = _lib, base, base.device
-        self.P, self.A, self.N = base.P, base.A, base.N
+        self.P, self.A, self.N, self.S = base.P, base.A, base.N, 8 * base.N
         assert base.dtype == torch.float32 and self.device.type == 'cuda' and len(base.layers) == 3
         keep = self.pack(base)
         self._keep = keep
@@ -1300,43 +1210,11 @@ class SmallworldV62Hip:
         assert tuple(base.w_st.shape) == (21, 48) and tuple(base.t_ppl.shape) == (31, 48) and tuple(L[0]['w1'].shape) == (192, 48)
         return [t.to(torch.float32).contiguous() for t in keep]
 
-    def _alloc(self, B):
-        self.maxB = B
-        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
-        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == self.N * 8
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
-        assert valids.shape == (B, self.A) and valids.is_cuda
-        self._lib.check(self._lib.lib().azg_nn_sw62_forward(p(boards), p(valids), self.ptrs, 3, self.A, self.P, B, p(self.pi), p(self.v),
-                                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
-
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
-
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+    def _ints(self):
+        return (3, self.A, self.P)
 
 
-class AkropolisV31:
+class AkropolisV31(_TorchNet):
     """akropolis/AkropolisNNet.py nn_version 31 (constructor :91-146, input slicing :377-388, forward :573-622) -- the net of all three
     shipped checkpoints (pretrained_{2,3,4}pl.pt).  Per player, the board [embed(descr) (3), height, tileID] -> conv3x3(5->8) + BN +
     Hardswish -> conv3x3(8->8) + BN + Hardswish on 13 x 13 (shared weights); s1 = Linear(15P->16)(scores), g1 = Hardswish(BN(Linear(2->8)
@@ -1391,11 +1269,6 @@ class AkropolisV31:
             setattr(self, n, getattr(self, n).to(self.device, dtype).contiguous())
         return self
 
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
-
     def context(self, x):
         """x [B][13][13][C] (self.dtype) -> s1 [B][16], g1 [B][8], f3 [B][CS][56]"""
         P, CS = self.P, self.CS
@@ -1432,20 +1305,12 @@ class AkropolisV31:
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class AkropolisV31Hip:
+class AkropolisV31Hip(_EngineNet):
     """AkropolisV31 (P = 2 / 3 / 4) evaluated by the engine's one-launch kernel (azg_nn_akr31_forward, csrc/nn_akropolis.hip.h: one
     workgroup per sample, one cell per lane, the whole forward and the masked softmax on the vector ALUs) instead of ~50 torch
     launches.  Wraps an AkropolisV31; static pi / v buffers (HIP-graph capture of the engine's rounds)."""
+    _FN = 'azg_nn_akr31_forward'
 
     @staticmethod
     def layout(P):
@@ -1497,7 +1362,6 @@ class AkropolisV31Hip:
         return out
 
     def __init__(self, base, max_batch=4096):
-        import ctypes as C
         from . import _lib
         self._lib, self.base, self.device = _lib, base, base.device
         self.P, self.A, self.S = base.P, base.A, base.S
@@ -1507,43 +1371,11 @@ class AkropolisV31Hip:
         self.ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in keep])
         self._alloc(max_batch)
 
-    def _alloc(self, B):
-        self.maxB = B
-        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
-        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == self.S
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
-        assert valids.shape == (B, self.A) and valids.is_cuda
-        self._lib.check(self._lib.lib().azg_nn_akr31_forward(p(boards), p(valids), self.ptrs, self.P, self.A, B, p(self.pi), p(self.v),
-                                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
-
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
-
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+    def _ints(self):
+        return (self.P, self.A)
 
 
-class BotanikV1x:
+class BotanikV1x(_TorchNet):
     """botanik/BotanikNNet.py nn_version 10 (:105-160) and 11 (:162-237), forward :251-292: the (66, 5, 7) board, rows 0..25 read.
     1-d branch: rows 0..5 as (C = 7, L = 30) -> first_layer_1d (Linear 7 -> 7 + BN) -> trunk_1d InvertedResidual1d(7, 21, 7, 30, ReLU, SE
     avg: the reference passes "RE" as use_se, which is truthy) -> per head InvertedResidual1d(7, 21, 7, 30, Hardswish, SE max) + Flatten +
@@ -1602,11 +1434,6 @@ class BotanikV1x:
         self.t = {k: v.to(self.device, dtype) for k, v in self.t.items()}
         return self
 
-    @classmethod
-    def from_npz(cls, path, **kw):
-        z = np.load(path)
-        return cls({k[3:]: z[k] for k in z.files if k.startswith('sd/')}, **kw)
-
     def _block1d(self, k, x, hs, maxpool):              # x [B, 7, 30]
         t, act = self.t, (F.hardswish if hs else F.relu)
         h = act(torch.einsum('ec,bcl->bel', t[k + 'We'], x) + t[k + 'be'][:, None])
@@ -1650,25 +1477,16 @@ class BotanikV1x:
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
 
-    def predict(self, board, valid_actions):
-        b = torch.from_numpy(np.ascontiguousarray(board, dtype=np.int8))[None].to(self.device)
-        va = torch.from_numpy(np.asarray(valid_actions).astype(np.bool_))[None].to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
-
-
-class BotanikV1xHip:
+class BotanikV1xHip(_EngineNet):
     """BotanikV1x (V10 or V11, A = 428) evaluated by the engine's one-launch kernel (azg_nn_bot_forward, csrc/nn_botanik.hip.h: the
     1-d branch on the vector ALUs, the machine branches' 1x1 convolutions and every policy Linear as f32 MFMA GEMMs, the depthwise 3x3 on
     the vector ALUs, final layers, masked softmax and tanh in the same launch).  Wraps a BotanikV1x; static pi / v buffers (HIP-graph
     capture of the engine's rounds)."""
+    _FN, S = 'azg_nn_bot_forward', 2310
     MBLOB = 24496
 
     def __init__(self, base, max_batch=4096):
-        import ctypes as C
         from . import _lib
         self._lib, self.base, self.device = _lib, base, base.device
         self.P, self.A, self.n_mach = base.P, base.A, base.n_mach
@@ -1721,40 +1539,8 @@ class BotanikV1xHip:
         assert keep[0].numel() == 56 + 3 * 1629 and keep[1].numel() == cls.MBLOB * base.n_mach and keep[9].numel() == 14
         return keep
 
-    def _alloc(self, B):
-        self.maxB = B
-        self.pi = torch.empty((B, self.A), dtype=torch.float32, device=self.device)
-        self.v = torch.empty((B, self.P), dtype=torch.float32, device=self.device)
-
-    def clone_buffers(self):
-        import copy
-        other = copy.copy(self)
-        other._alloc(self.maxB)
-        return other
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        import ctypes as C
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda and boards.shape[1] == 2310
-        valids = (valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)).contiguous()
-        assert valids.shape == (B, self.A) and valids.is_cuda
-        self._lib.check(self._lib.lib().azg_nn_bot_forward(p(boards), p(valids), self.ptrs, self.n_mach, self.P, self.A, B, p(self.pi),
-                                                           p(self.v), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return self.pi[:B], self.v[:B]
-
-    def predict_batch(self, boards, valids):
-        return self.forward(boards, valids)
-
-    def predict(self, board, valid_actions):
-        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
-        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
-        pi, v = self.forward(b, va)
-        return pi[0].cpu().numpy(), v[0].cpu().numpy()
+    def _ints(self):
+        return (self.n_mach, self.P, self.A)
 
 
 class TorchModuleEvaluator:

@@ -13,6 +13,7 @@ The module is one of azg_amd.train's trainable nets (same parameter names as the
 with strict=True); inference runs on the engine's one-launch MFMA kernels (azg_amd.nnet.*Hip) with the module's current
 weights (BatchNorm folded) -- the reference exports to ONNX-runtime on one CPU core at this point (:232-277).  The evaluator is
 rebuilt lazily after every weight change (train / load_checkpoint).  `predict_batch` is the batched form the engine uses."""
+import collections
 import copy
 import os
 import pickle
@@ -30,60 +31,65 @@ _DEFAULT_VERSION = {(_lib.SPLENDOR, 2): 80, (_lib.SPLENDOR, 3): 80, (_lib.SPLEND
                     (_lib.SANTORINI, 1): 89, (_lib.SANTORINI, 11): 78}
 
 
+def _engine(hip, base, num_players=True):
+    """evaluator factory (state_dict, game, device, max_batch) -> hip(base(state_dict[, num_players=P], device=...), max_batch=...)"""
+    def make(sd, game, device, max_batch):
+        kw = dict(num_players=game.P) if num_players else {}
+        return hip(base(sd, device=device, **kw), max_batch=max_batch)
+    return make
+
+
+def _splendor_v80(sd, game, device, max_batch):
+    if game.P == 2:
+        return _nn.SplendorV80Hip(sd, num_players=2, device=device, max_batch=max_batch)
+    return _nn.MobileNet1dHip(_nn.SplendorV80(sd, num_players=game.P, device=device), max_batch=max_batch)
+
+
+EngineNet = collections.namedtuple('EngineNet', 'game variants version module evaluator')
+# the engine nets: game id, game variants (None = any), nn_version, trainable module (azg_amd.train) and the factory of its engine-kernel
+# evaluator.  (Santorini 88 is a different trunk in the reference, SantoriniNNet.py:167-192: not built)
+ENGINE_NETS = (
+    EngineNet(_lib.SPLENDOR, None, 80, _train.SplendorV80Module, _splendor_v80),
+    EngineNet(_lib.AZUL, None, 84, _train.AzulV84Module, _engine(_nn.MobileNet1dHip, _nn.AzulV84)),
+    EngineNet(_lib.SANTORINI, (1,), 89, _train.SantoriniV89Module, _engine(_nn.SantoriniV89Hip, _nn.SantoriniV89, num_players=False)),
+    EngineNet(_lib.SANTORINI, (11,), 78, _train.SantoriniV78Module, _engine(_nn.SantoriniV78Hip, _nn.SantoriniV78, num_players=False)),
+    EngineNet(_lib.ABALONE, None, 21, _train.AbaloneV21Module, _engine(_nn.AbaloneV21Hip, _nn.AbaloneV21, num_players=False)),
+    EngineNet(_lib.SMALLWORLD, None, 62, _train.SmallworldV62Module, _engine(_nn.SmallworldV62Hip, _nn.SmallworldV62)),
+    EngineNet(_lib.AKROPOLIS, None, 31, _train.AkropolisV31Module, _engine(_nn.AkropolisV31Hip, _nn.AkropolisV31)),
+    EngineNet(_lib.MINIVILLES, None, 82, _train.MinivillesV82Module, _engine(_nn.MobileNet1dHip, _nn.MobileNet1d)),
+    EngineNet(_lib.TLP, None, 83, _train.TLPV83Module, _engine(_nn.MobileNet1dHip, _nn.MobileNet1d)),
+    EngineNet(_lib.BOTANIK, None, 10, _train.BotanikV10Module, _engine(_nn.BotanikV1xHip, _nn.BotanikV1x, num_players=False)),
+    EngineNet(_lib.BOTANIK, None, 11, _train.BotanikV11Module, _engine(_nn.BotanikV1xHip, _nn.BotanikV1x, num_players=False)),
+)
+_BY_MODULE = {r.module: r for r in ENGINE_NETS}
+
+
 def _module_for(game, version, dropout):
-    gid, P, A = game.GAME_ID, game.P, game.A
-    if gid == _lib.SPLENDOR and version == 80:
-        return _train.SplendorV80Module(P, A, dropout)
-    if gid == _lib.AZUL and version == 84:
-        return _train.AzulV84Module(P, A, dropout)
-    if gid == _lib.SANTORINI and version == 89 and game.variant == 1:      # (88 is a different trunk in the reference, SantoriniNNet.py:167-192: not built)
-        return _train.SantoriniV89Module(P, A, dropout)
-    if gid == _lib.SANTORINI and version == 78 and game.variant == 11:
-        return _train.SantoriniV78Module(P, A, dropout)
-    if gid == _lib.ABALONE and version == 21:
-        return _train.AbaloneV21Module(P, A, dropout)
-    if gid == _lib.SMALLWORLD and version == 62:
-        return _train.SmallworldV62Module(P, A, dropout)
-    if gid == _lib.AKROPOLIS and version == 31:
-        return _train.AkropolisV31Module(P, A, dropout)
-    if gid == _lib.MINIVILLES and version == 82:
-        return _train.MinivillesV82Module(P, A, dropout)
-    if gid == _lib.TLP and version == 83:
-        return _train.TLPV83Module(P, A, dropout)
-    if gid == _lib.BOTANIK and version in (10, 11):
-        return (_train.BotanikV10Module if version == 10 else _train.BotanikV11Module)(P, A, dropout)
-    raise ValueError('nn_version %r is not built for this game (engine nets: Splendor 80, Azul 84, Santorini 89 no-gods / 78 with gods, '
-                     'Abalone 21, Smallworld 62, Akropolis 31, Minivilles 82, The Little Prince 83, Botanik 10 / 11)'
-                     % (version,))
+    for r in ENGINE_NETS:
+        if r.game == game.GAME_ID and r.version == version and (r.variants is None or game.variant in r.variants):
+            return r.module(game.P, game.A, dropout)
+    raise ValueError('nn_version %r is not built for this game (engine nets: %s)' % (version, ', '.join(
+        '%s%s' % (r.module.__name__[:-len('Module')], '' if r.variants is None else ' (variant %s)' % '/'.join(map(str, r.variants)))
+        for r in ENGINE_NETS)))
+
+
+def _engine_net(module):
+    """the table row of the first class in module's MRO that has one (a subclass of an engine module keeps its engine net), or None"""
+    return next((_BY_MODULE[c] for c in type(module).__mro__ if c in _BY_MODULE), None)
+
+
+def is_engine_module(module):
+    return _engine_net(module) is not None
 
 
 def evaluator_for(module, game, max_batch):
-    """engine-kernel evaluator (one launch per leaf batch) of a trainable module's current weights"""
-    sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
-    dev, ver = str(game.device), getattr(module, 'version', 80)
-    if not isinstance(module, (_train.SplendorV80Module, _train.AzulV84Module, _train.SantoriniV89Module, _train.SantoriniV78Module,
-                               _train.AbaloneV21Module, _train.SmallworldV62Module, _train.AkropolisV31Module, _train.MinivillesV82Module,
-                               _train.TLPV83Module, _train.BotanikV10Module)):
+    """engine-kernel evaluator (one launch per leaf batch) of a trainable module's current weights; any other torch module is evaluated
+    by PyTorch-ROCm (nnet.TorchModuleEvaluator)"""
+    row = _engine_net(module)
+    if row is None:
         return _nn.TorchModuleEvaluator(module, game, max_batch)
-    if isinstance(module, _train.BotanikV10Module):                 # V10 and its subclass V11
-        return _nn.BotanikV1xHip(_nn.BotanikV1x(sd, device=dev), max_batch=max_batch)
-    if isinstance(module, (_train.MinivillesV82Module, _train.TLPV83Module)):
-        return _nn.MobileNet1dHip(_nn.MobileNet1d(sd, num_players=game.P, device=dev), max_batch=max_batch)
-    if ver == 31:
-        return _nn.AkropolisV31Hip(_nn.AkropolisV31(sd, num_players=game.P, device=dev), max_batch=max_batch)
-    if ver == 62:
-        return _nn.SmallworldV62Hip(_nn.SmallworldV62(sd, num_players=game.P, device=dev), max_batch=max_batch)
-    if ver == 21:
-        return _nn.AbaloneV21Hip(_nn.AbaloneV21(sd, device=dev), max_batch=max_batch)
-    if ver == 84:
-        return _nn.MobileNet1dHip(_nn.AzulV84(sd, num_players=game.P, device=dev), max_batch=max_batch)
-    if ver == 89:
-        return _nn.SantoriniV89Hip(_nn.SantoriniV89(sd, device=dev), max_batch=max_batch)
-    if ver == 78:
-        return _nn.SantoriniV78Hip(_nn.SantoriniV78(sd, device=dev), max_batch=max_batch)
-    if game.P == 2:
-        return _nn.SplendorV80Hip(sd, num_players=2, device=dev, max_batch=max_batch)
-    return _nn.MobileNet1dHip(_nn.SplendorV80(sd, num_players=game.P, device=dev), max_batch=max_batch)
+    sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
+    return row.evaluator(sd, game, str(game.device), max_batch)
 
 
 def decode_examples(examples):
