@@ -26,6 +26,8 @@
 #include "game_santorini.hip.h"
 #include "game_azul.hip.h"
 #include "game_smallworld.hip.h"
+#include "game_minivilles.hip.h"
+#include "game_tlp.hip.h"
 
 using namespace azg;
 

@@ -559,8 +559,8 @@ struct NetC5 {                                 // Santorini no-gods: k_conv5_net
     }
 };
 template <class CF, class GAME>
-struct NetMb1d {                               // Splendor 3 / 4 players (8 leaves per forward), Azul (16): k_mb1d_net<CF, true>'s body
-    using G = GAME;
+struct NetMb1d {                               // Splendor 3 / 4 players (8 leaves per forward), Azul (16), Minivilles (16), TLP 3 (8) / 4, 5 (6):
+    using G = GAME;                            // k_mb1d_net<CF, true>'s body
     static constexpr int BS = CF::NS, LDS = (CF::LDS_FLOATS * 4 + 255) / 256 * 256;
     static __device__ __forceinline__ void run(uint8_t* lds, AsyncArgsC A, const int* sidx, unsigned long long* smask) {
         mb1d_net_body<CF, true, true, AsyncLeaf<G>::STRIDE, AsyncLeaf<G>::MASK_OFF>((float*)lds, &A->MB, A->aleaf, (const uint8_t*)A->aleaf, A->F.T, A->pi, A->v, 0,
@@ -634,6 +634,27 @@ struct NetSw62 {                               // Smallworld 2 / 3 / 4 players: 
 using NetSpl3 = NetMb1d<CfgSplendor3, SplendorDev<3>>;
 using NetSpl4 = NetMb1d<CfgSplendor4, SplendorDev<4>>;
 using NetAzul = NetMb1d<CfgAzul, AzulDev>;
+template <int NPL> struct MinivillesCfg;
+template <> struct MinivillesCfg<2> { using type = CfgMinivilles2; };
+template <> struct MinivillesCfg<3> { using type = CfgMinivilles3; };
+template <> struct MinivillesCfg<4> { using type = CfgMinivilles4; };
+template <int NPL> struct TLPCfg;
+template <> struct TLPCfg<3> { using type = CfgTLP3; };
+template <> struct TLPCfg<4> { using type = CfgTLP4; };
+template <> struct TLPCfg<5> { using type = CfgTLP5; };
+template <int NPL> using NetMv = NetMb1d<typename MinivillesCfg<NPL>::type, MinivillesDev<NPL>>;
+template <int NPL> using NetTlp = NetMb1d<typename TLPCfg<NPL>::type, TLPDev<NPL>>;
+// the geometry is the game's: the net's A / P are the game's, its input (C channels x L tokens) is the canonical board's S bytes, and the
+// forward with its batch descriptor fits the CU's LDS (a net workgroup per CU)
+template <class NET, class CF>
+constexpr bool mb1d_fits() {
+    using G = typename NET::G;
+    return G::A == CF::A && G::P == CF::P && G::S == CF::L * CF::C && NET::LDS + ASYNC_DESC_BYTES <= 160 * 1024;
+}
+static_assert(mb1d_fits<NetMv<2>, CfgMinivilles2>() && mb1d_fits<NetMv<3>, CfgMinivilles3>() && mb1d_fits<NetMv<4>, CfgMinivilles4>(),
+              "the Minivilles V82 geometry is the game's and fits the LDS");
+static_assert(mb1d_fits<NetTlp<3>, CfgTLP3>() && mb1d_fits<NetTlp<4>, CfgTLP4>() && mb1d_fits<NetTlp<5>, CfgTLP5>(),
+              "the TLP V83 geometry is the game's and fits the LDS");
 static_assert(NetV80::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetC5::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSpl4::LDS + ASYNC_DESC_BYTES <= 160 * 1024 &&
               NetSpl3::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetAzul::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSw62<2>::LDS + ASYNC_DESC_BYTES <= 160 * 1024 &&
               NetSw62<3>::LDS + ASYNC_DESC_BYTES <= 160 * 1024 && NetSw62<4>::LDS + ASYNC_DESC_BYTES <= 160 * 1024, "net LDS + batch descriptor");
@@ -822,6 +843,7 @@ __global__ __launch_bounds__(768) void k_async_net(const AsyncArgs* args) {
 // because they want different code generation (build.py)
 template <class G>
 static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
+    static_assert(azg::ASYNC_SEL_WAVES * azg::RoundLds<G>::STRIDE + sizeof(azg::AsyncSelLds) <= 160 * 1024, "the descent workgroup's LDS fits the CU");
     static bool attr[64];                       // (per device: a function attribute belongs to the device that was current when it was set)
     int device = 0;
     HIPCHK(hipGetDevice(&device));
@@ -834,7 +856,8 @@ static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStrea
     return 0;
 }
 // net_kind: 0 = Splendor 2 players (V80), 1 = Santorini no-gods (V89), 2 / 3 = Splendor 3 / 4 players, 4 = Azul (MobileNet-1d), 5 = Santorini with gods,
-// 6 / 7 / 8 = Smallworld 2 / 3 / 4 players (V62)
+// 6 / 7 / 8 = Smallworld 2 / 3 / 4 players (V62), 9 / 10 / 11 = Minivilles 2 / 3 / 4 players, 12 / 13 / 14 = The Little Prince 3 / 4 / 5 players
+// (MobileNet-1d; the first STOCHASTIC games here: the descent draws their dice / market refills from the tree's stream)
 int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
 #ifdef AZG_ASYNC_ONLY_KIND      /* code-generation experiments: one game's kernel only */
     if (net_kind != AZG_ASYNC_ONLY_KIND) return -1;
@@ -852,6 +875,12 @@ int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_se
         case 6: return async_launch_select<azg::SmallworldDev<2>>(devbuf, n_sel, s);
         case 7: return async_launch_select<azg::SmallworldDev<3>>(devbuf, n_sel, s);
         case 8: return async_launch_select<azg::SmallworldDev<4>>(devbuf, n_sel, s);
+        case 9: return async_launch_select<azg::MinivillesDev<2>>(devbuf, n_sel, s);
+        case 10: return async_launch_select<azg::MinivillesDev<3>>(devbuf, n_sel, s);
+        case 11: return async_launch_select<azg::MinivillesDev<4>>(devbuf, n_sel, s);
+        case 12: return async_launch_select<azg::TLPDev<3>>(devbuf, n_sel, s);
+        case 13: return async_launch_select<azg::TLPDev<4>>(devbuf, n_sel, s);
+        case 14: return async_launch_select<azg::TLPDev<5>>(devbuf, n_sel, s);
         default: return -1;
     }
 #endif
@@ -978,12 +1007,70 @@ static int async_net_attr() {
     HIPCHK(hipFuncSetAttribute((const void*)k_async_net<NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return 0;
 }
+// One row per pipeline kind: the forest it serves (variant -1: any), what a refusal of another forest says (nullptr: "the geometry does not
+// match the forest's game" with both named), the leaf record's stride, the samples of a forward, the weight table the net reads, and the
+// default split of the CUs -- the net's share in 256ths, and whether the descent side is then grown until no workgroup owns more than 128
+// trees.  (The kinds are the cases of the two launch switches below and of azg_async_launch_select.)
+enum AsyncWt { WT_V80, WT_C5, WT_MB, WT_SW };
+struct AsyncKind { int game, variant; const char* name; const char* only; int leaf_stride, bs, wt, net_256; bool cap_trees; };
+static_assert(AsyncLeaf<SplendorDev<2>>::STRIDE == H2_AL_STRIDE && AsyncLeaf<SplendorDev<2>>::MASK_OFF == H2_AL_MASK, "leaf record layout shared with the net kernel");
+static_assert(AsyncLeaf<SantoriniDev<1>>::STRIDE == C5_AL_STRIDE && AsyncLeaf<SantoriniDev<1>>::MASK_OFF == C5_AL_MASK, "leaf record layout shared with the net kernel");
+// Default splits.  V80: measured at 4096 x 800 (round 6, descent 19.9 us: see DESIGN.md 3.6); V89: round 5 a forward of 8
+// leaves cost ~75 us of a CU, a descent ~33 us of a sixteenth of one: 13 / 16 for the net (208 + 48 -> 28.8 k env-steps/s, 216 + 40
+// 24.5 k, 204 + 52 28.7 k, 200 + 56 28.3 k; two kernels 26.5 k); round 6 with the forward at 63-70 us (nn_tid): 3 / 4 (208 + 48 -> 26.8 k,
+// 200 + 56 30.5 k, 192 + 64 32.4 k, 184 + 72 31.7 k, 176 + 80 30.7 k; with the claim path off scratch 192 + 64 33.2 k, 196 + 60 33.9 k,
+// 200 + 56 33.6 k: 49 / 64); Splendor 3 / 4 players (forward 55-59 us per 8 leaves, descent 27 us):
+// round 5 25 / 32 for the net (4 players: 200 + 56 -> 35.8 k, 208 + 48 33.1 k, 192 + 64 34.6 k), round 6 with the descent at 22 us
+// 13 / 16 (200 + 56 -> 38.8 k, 208 + 48 40.1 k, 216 + 40 36.1 k); Azul (descent-heavy, forward 29 us per 16):
+// round 5 3 / 8 (96 + 160 -> 70.4 k; 112 + 144 68.6 k, 88 + 168 66.3 k), round 6 13 / 32 (96 + 160 69.9 k, 104 + 152 72.3 k).
+// Smallworld + V62 (forward of 4 / 3 / 2 leaves 157 / 128 / 122 us, descent 36-48 us): 7 / 8 for the net, and never fewer
+// descent workgroups than the 128 trees each can own need.  Measured at 200 simulations, 2 players x 1024 games: 240 + 16 -> 16.7 k plies/s
+// (descent-bound: the waves 94 % busy, trees wait 24 us for one), 224 + 32 24.8 k, 208 + 48 25.4 k; 3 / 4 players x 512: 224 + 32 +4 / +6 %
+// over 240 + 16.
+// Minivilles / TLP + MobileNet-1d (forward of 16 / 8 leaves 23 / 35 us, descent 17-18 / 28-33 us): 1 / 2 and 5 / 8 for the net, with the
+// 128-tree rule (n_net is further capped at ceil(T / leaves per forward)).  Measured at 200 simulations (plies/s, net + descent CUs; profiles/
+// r08_stochastic_pipeline.md): Minivilles 2 players x 1024 games 16 + 240 -> 54.0 k, 32 + 224 104.4 k, 48 + 208 104.8 k, 64 + 192 109.5 k (two
+// kernels 77.4 k); x 4096 games 64 + 192 212 k, 96 + 160 308 k, 128 + 128 363 k, 160 + 96 293 k, 192 + 64 199 k (two kernels 238 k).  TLP 3
+// players x 1024: 32 + 224 35.0 k, 64 + 192 69.4 k, 96 + 160 76.2 k, 128 + 128 75.7 k (two kernels 71.1 k); x 4096: 96 + 160 108 k, 128 + 128
+// 144 k, 160 + 96 173 k, 192 + 64 139 k (two kernels 171 k).
+// The hash-net costs next to nothing: a sixteenth, whatever the kind.
+#ifndef AZG_MV_NET_SHARE_256
+#define AZG_MV_NET_SHARE_256 128            /* default net share of the CUs for Minivilles 2 - 4 players + V82, in 256ths */
+#endif
+#ifndef AZG_TLP_NET_SHARE_256
+#define AZG_TLP_NET_SHARE_256 160           /* default net share of the CUs for The Little Prince 3 - 5 players + V83, in 256ths */
+#endif
+static const AsyncKind ASYNC_KINDS[] = {
+    {AZG_SPLENDOR, 2, "Splendor 2 players", "Splendor 2 players only (the V80 geometry of nn_v80_h2.hip.h)", H2_AL_STRIDE, NetV80::BS, WT_V80, AZG_V80_NET_SHARE_256, false},
+    {AZG_SANTORINI, 1, "Santorini without gods", "Santorini without gods only (the V89 geometry of nn_conv5x5.hip.h)", C5_AL_STRIDE, NetC5::BS, WT_C5, 196, false},
+    {AZG_SPLENDOR, 3, "Splendor 3 players", nullptr, AsyncLeaf<SplendorDev<3>>::STRIDE, NetSpl3::BS, WT_MB, 208, false},
+    {AZG_SPLENDOR, 4, "Splendor 4 players", nullptr, AsyncLeaf<SplendorDev<4>>::STRIDE, NetSpl4::BS, WT_MB, 208, false},
+    {AZG_AZUL, -1, "Azul", nullptr, AsyncLeaf<AzulDev>::STRIDE, NetAzul::BS, WT_MB, 104, false},
+    {AZG_SANTORINI, 11, "Santorini with gods", "Santorini with gods only", AsyncLeaf<SantoriniDev<11>>::STRIDE, 16, WT_C5, 196, false},
+    {AZG_SMALLWORLD, 2, "Smallworld 2 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<2>>::STRIDE, NetSw62<2>::BS, WT_SW, 224, true},
+    {AZG_SMALLWORLD, 3, "Smallworld 3 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<3>>::STRIDE, NetSw62<3>::BS, WT_SW, 224, true},
+    {AZG_SMALLWORLD, 4, "Smallworld 4 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<4>>::STRIDE, NetSw62<4>::BS, WT_SW, 224, true},
+    {AZG_MINIVILLES, 2, "Minivilles 2 players", nullptr, AsyncLeaf<MinivillesDev<2>>::STRIDE, NetMv<2>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
+    {AZG_MINIVILLES, 3, "Minivilles 3 players", nullptr, AsyncLeaf<MinivillesDev<3>>::STRIDE, NetMv<3>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
+    {AZG_MINIVILLES, 4, "Minivilles 4 players", nullptr, AsyncLeaf<MinivillesDev<4>>::STRIDE, NetMv<4>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
+    {AZG_TLP, 3, "The Little Prince 3 players", nullptr, AsyncLeaf<TLPDev<3>>::STRIDE, NetTlp<3>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
+    {AZG_TLP, 4, "The Little Prince 4 players", nullptr, AsyncLeaf<TLPDev<4>>::STRIDE, NetTlp<4>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
+    {AZG_TLP, 5, "The Little Prince 5 players", nullptr, AsyncLeaf<TLPDev<5>>::STRIDE, NetTlp<5>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
+};
+constexpr int ASYNC_NKINDS = (int)(sizeof(ASYNC_KINDS) / sizeof(ASYNC_KINDS[0]));
+static std::string async_forest_name(int game, int variant) {
+    static const char* const names[] = {"Splendor", "Santorini", "Azul", "Minivilles", "Abalone", "The Little Prince", "Botanik", "Akropolis", "Smallworld"};
+    std::string n = game >= 0 && game < (int)(sizeof(names) / sizeof(names[0])) ? names[game] : "game " + std::to_string(game);
+    return n + " (variant " + std::to_string(variant) + ")";
+}
 static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v,
                              int noise_stride, const void* const* w, const float* descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                              int shared_budget, void* stream) {
     const std::string me(who);
-    if (!f || !leaf_valid || !needs_eval || !pi || !v || (!hash && (!w || (kind < 6 && !descale)))) return fail(me + ": null argument");
-    if (!hash && kind >= 6)
+    if (kind < 0 || kind >= ASYNC_NKINDS) return fail(me + ": unknown pipeline kind");
+    const AsyncKind& K = ASYNC_KINDS[kind];
+    if (!f || !leaf_valid || !needs_eval || !pi || !v || (!hash && (!w || (K.wt != WT_SW && !descale)))) return fail(me + ": null argument");
+    if (!hash && K.wt == WT_SW)
         for (int i = 0; i < SW_NW; i++)
             if (!w[i]) return fail(me + ": null weight pointer");
     if (rounds < 0 || (rounds == 0 && shared_budget)) return 0;       // (per-tree budgets: rounds == 0 = only what earlier launches left over)
@@ -992,20 +1079,11 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
     int game = 0, variant = 0;
     double alpha = 0.0;
     const ForestDev* dev = azg_forest_dev_internal(f, &game, &variant, &alpha);
-    if (kind == 0 && (game != AZG_SPLENDOR || variant != 2)) return fail(me + ": Splendor 2 players only (the V80 geometry of nn_v80_h2.hip.h)");
-    if (kind == 1 && (game != AZG_SANTORINI || variant != 1)) return fail(me + ": Santorini without gods only (the V89 geometry of nn_conv5x5.hip.h)");
-    if ((kind == 2 || kind == 3) && (game != AZG_SPLENDOR || variant != kind + 1)) return fail(me + ": the geometry does not match the forest's game");
-    if (kind == 4 && game != AZG_AZUL) return fail(me + ": the geometry does not match the forest's game");
-    if (kind == 5 && (game != AZG_SANTORINI || variant != 11)) return fail(me + ": Santorini with gods only");
-    if (kind >= 6 && (game != AZG_SMALLWORLD || variant != kind - 4)) return fail(me + ": Smallworld only (the V62 geometry of nn_smallworld.hip.h)");
-    static_assert(AsyncLeaf<SplendorDev<2>>::STRIDE == H2_AL_STRIDE && AsyncLeaf<SplendorDev<2>>::MASK_OFF == H2_AL_MASK, "leaf record layout shared with the net kernel");
-    static_assert(AsyncLeaf<SantoriniDev<1>>::STRIDE == C5_AL_STRIDE && AsyncLeaf<SantoriniDev<1>>::MASK_OFF == C5_AL_MASK, "leaf record layout shared with the net kernel");
-    const int leaf_strides[9] = {H2_AL_STRIDE, C5_AL_STRIDE, AsyncLeaf<SplendorDev<3>>::STRIDE, AsyncLeaf<SplendorDev<4>>::STRIDE, AsyncLeaf<AzulDev>::STRIDE,
-                                 AsyncLeaf<SantoriniDev<11>>::STRIDE, AsyncLeaf<SmallworldDev<2>>::STRIDE, AsyncLeaf<SmallworldDev<3>>::STRIDE,
-                                 AsyncLeaf<SmallworldDev<4>>::STRIDE};
-    const int batch[9] = {NetV80::BS, NetC5::BS, NetSpl3::BS, NetSpl4::BS, NetAzul::BS, 16, NetSw62<2>::BS, NetSw62<3>::BS, NetSw62<4>::BS};
-    if (kind < 0 || kind >= 9) return fail(me + ": unknown pipeline kind");
-    const int leaf_stride = leaf_strides[kind], bs = hash ? 16 : batch[kind];
+    if (game != K.game || (K.variant >= 0 && variant != K.variant)) {
+        if (K.only) return fail(me + ": " + K.only);
+        return fail(me + ": the geometry does not match the forest's game (the geometry is " + K.name + "'s, the forest is " + async_forest_name(game, variant) + ")");
+    }
+    const int leaf_stride = K.leaf_stride, bs = hash ? 16 : K.bs;
     int device = 0;
     HIPCHK(hipGetDevice(&device));
     if (device < 0 || device >= ASYNC_MAX_DEVICES) return fail(me + ": device index out of range");
@@ -1019,30 +1097,17 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
         if (async_net_attr<NetV80>() || async_net_attr<NetC5>() || async_net_attr<NetSpl3>() || async_net_attr<NetSpl4>() || async_net_attr<NetAzul>() ||
-            async_net_attr<NetSw62<2>>() || async_net_attr<NetSw62<3>>() || async_net_attr<NetSw62<4>>())
+            async_net_attr<NetSw62<2>>() || async_net_attr<NetSw62<3>>() || async_net_attr<NetSw62<4>>() || async_net_attr<NetMv<2>>() ||
+            async_net_attr<NetMv<3>>() || async_net_attr<NetMv<4>>() || async_net_attr<NetTlp<3>>() || async_net_attr<NetTlp<4>>() || async_net_attr<NetTlp<5>>())
             return -1;
         D.net_stream = a; D.sel_stream = b; D.n_cu = prop.multiProcessorCount;
     }
     const int n_cu = D.n_cu;
     const int T = dev->T;
     if (n_net <= 0 || n_sel <= 0) {
-        // default split of the CUs.  V80: measured at 4096 x 800 (round 6, descent 19.9 us: see DESIGN.md 3.6); V89: round 5 a forward of 8
-        // leaves cost ~75 us of a CU, a descent ~33 us of a sixteenth of one: 13 / 16 for the net (208 + 48 -> 28.8 k env-steps/s, 216 + 40
-        // 24.5 k, 204 + 52 28.7 k, 200 + 56 28.3 k; two kernels 26.5 k); round 6 with the forward at 63-70 us (nn_tid): 3 / 4 (208 + 48 -> 26.8 k,
-        // 200 + 56 30.5 k, 192 + 64 32.4 k, 184 + 72 31.7 k, 176 + 80 30.7 k; with the claim path off scratch 192 + 64 33.2 k, 196 + 60 33.9 k,
-        // 200 + 56 33.6 k: 49 / 64); Splendor 3 / 4 players (forward 55-59 us per 8 leaves, descent 27 us):
-        // round 5 25 / 32 for the net (4 players: 200 + 56 -> 35.8 k, 208 + 48 33.1 k, 192 + 64 34.6 k), round 6 with the descent at 22 us
-        // 13 / 16 (200 + 56 -> 38.8 k, 208 + 48 40.1 k, 216 + 40 36.1 k); Azul (descent-heavy, forward 29 us per 16):
-        // round 5 3 / 8 (96 + 160 -> 70.4 k; 112 + 144 68.6 k, 88 + 168 66.3 k), round 6 13 / 32 (96 + 160 69.9 k, 104 + 152 72.3 k).  The hash-net costs next to nothing: a sixteenth.
-        n_net = hash ? (n_cu / 16 > 0 ? n_cu / 16 : 1) : kind == 0 ? n_cu * AZG_V80_NET_SHARE_256 / 256 : kind == 4 ? n_cu * 13 / 32 : (kind == 2 || kind == 3) ? n_cu * 13 / 16 : n_cu * 49 / 64;
-        // Smallworld + V62 (forward of 4 / 3 / 2 leaves 157 / 128 / 122 us, descent 36-48 us): 7 / 8 for the net, and never fewer
-        // descent workgroups than the 128 trees each can own need.  Measured at 200 simulations, 2 players x 1024 games: 240 + 16 -> 16.7 k plies/s
-        // (descent-bound: the waves 94 % busy, trees wait 24 us for one), 224 + 32 24.8 k, 208 + 48 25.4 k; 3 / 4 players x 512: 224 + 32 +4 / +6 %
-        // over 240 + 16
-        if (kind >= 6 && !hash) {
-            n_net = n_cu * 7 / 8;
-            if ((n_cu - n_net) * ASYNC_RS < T) { n_net = n_cu - (T + ASYNC_RS - 1) / ASYNC_RS; n_net = n_net < 1 ? 1 : n_net; }
-        }
+        // default split of the CUs: the kind's row of ASYNC_KINDS (the measurements are recorded above the table)
+        n_net = hash ? (n_cu / 16 > 0 ? n_cu / 16 : 1) : n_cu * K.net_256 / 256;
+        if (K.cap_trees && !hash && (n_cu - n_net) * ASYNC_RS < T) { n_net = n_cu - (T + ASYNC_RS - 1) / ASYNC_RS; n_net = n_net < 1 ? 1 : n_net; }
         n_sel = n_cu - n_net;
     }
     if (n_sel > T) n_sel = T;
@@ -1093,12 +1158,12 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
     // inside a launch -- but a launch ends only when every tree has had its calls, and a tree whose simulations all end on terminal nodes
     // would otherwise run its whole search inside ONE call: measured 4.1 ms launches of 48 rounds where the mean tree needs 3.4 ms)
     if (hash) {
-    } else if (kind == 0) want.W = h2_weights(w, descale);
-    else if (kind >= 6) {                             // the 25 pointers of azg_nn_sw62_forward, in the order of Sw62NetW
+    } else if (K.wt == WT_V80) want.W = h2_weights(w, descale);
+    else if (K.wt == WT_SW) {                         // the 25 pointers of azg_nn_sw62_forward, in the order of Sw62NetW
         static_assert(sizeof(Sw62NetW) == SW_NW * sizeof(const float*), "Sw62NetW is the 25-pointer table");
         memcpy(&want.SW, w, sizeof(Sw62NetW));
     }
-    else if (kind >= 2) {                             // the 43-pointer table + 16 descale factors of azg_nn_mb1d_forward_h2
+    else if (K.wt == WT_MB) {                         // the 43-pointer table + 16 descale factors of azg_nn_mb1d_forward_h2
         const float* const* wf = (const float* const*)w;
         Mb1dNetW& N = want.MB;
         for (int i = 0; i < 16; i++) N.ds[i] = descale[i];
@@ -1163,6 +1228,12 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
             case 6: rc = async_launch_net<NetHash<SmallworldDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
             case 7: rc = async_launch_net<NetHash<SmallworldDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
             case 8: rc = async_launch_net<NetHash<SmallworldDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 9: rc = async_launch_net<NetHash<MinivillesDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 10: rc = async_launch_net<NetHash<MinivillesDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 11: rc = async_launch_net<NetHash<MinivillesDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 12: rc = async_launch_net<NetHash<TLPDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 13: rc = async_launch_net<NetHash<TLPDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
+            case 14: rc = async_launch_net<NetHash<TLPDev<5>>>(sl->devbuf, n_net, D.net_stream); break;
 #ifdef AZG_ASYNC_SANTORINI11
             case 5: rc = async_launch_net<NetHash<SantoriniDev<11>>>(sl->devbuf, n_net, D.net_stream); break;
 #endif
@@ -1178,6 +1249,12 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
             case 6: rc = async_launch_net<NetSw62<2>>(sl->devbuf, n_net, D.net_stream); break;
             case 7: rc = async_launch_net<NetSw62<3>>(sl->devbuf, n_net, D.net_stream); break;
             case 8: rc = async_launch_net<NetSw62<4>>(sl->devbuf, n_net, D.net_stream); break;
+            case 9: rc = async_launch_net<NetMv<2>>(sl->devbuf, n_net, D.net_stream); break;
+            case 10: rc = async_launch_net<NetMv<3>>(sl->devbuf, n_net, D.net_stream); break;
+            case 11: rc = async_launch_net<NetMv<4>>(sl->devbuf, n_net, D.net_stream); break;
+            case 12: rc = async_launch_net<NetTlp<3>>(sl->devbuf, n_net, D.net_stream); break;
+            case 13: rc = async_launch_net<NetTlp<4>>(sl->devbuf, n_net, D.net_stream); break;
+            case 14: rc = async_launch_net<NetTlp<5>>(sl->devbuf, n_net, D.net_stream); break;
             default: return fail(me + ": no engine net for this game in the pipeline");
         }
     }
@@ -1201,12 +1278,27 @@ extern "C" int azg_forest_async_rounds_v80_h2(azg_forest* f, uint8_t* leaf_valid
     return async_rounds_impl("azg_forest_async_rounds_v80_h2", 0, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, w, descale, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }
-// include/azg.h: the pipeline for Splendor 3 / 4 players and Azul with their MobileNet-1d nets (geometry = AZG_NET_* of azg_nn_mb1d_forward_h2)
+// include/azg.h: the pipeline for Splendor 3 / 4 players, Azul, Minivilles 2 - 4 players and The Little Prince 3 - 5 players with their MobileNet-1d
+// nets (geometry = AZG_NET_* of azg_nn_mb1d_forward_h2)
 extern "C" int azg_forest_async_rounds_mb1d_h2(azg_forest* f, int geometry, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
                                                const void* const* w, const float* descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                                                int shared_budget, void* stream) {
-    const int kind = geometry == AZG_NET_SPLENDOR3 ? 2 : geometry == AZG_NET_SPLENDOR4 ? 3 : geometry == AZG_NET_AZUL ? 4 : -1;
-    if (kind < 0) return fail("azg_forest_async_rounds_mb1d_h2: geometry must be AZG_NET_SPLENDOR3, AZG_NET_SPLENDOR4 or AZG_NET_AZUL");
+    int kind = -1;
+    switch (geometry) {
+        case AZG_NET_SPLENDOR3: kind = 2; break;
+        case AZG_NET_SPLENDOR4: kind = 3; break;
+        case AZG_NET_AZUL: kind = 4; break;
+        case AZG_NET_MINIVILLES2: kind = 9; break;
+        case AZG_NET_MINIVILLES3: kind = 10; break;
+        case AZG_NET_MINIVILLES4: kind = 11; break;
+        case AZG_NET_TLP3: kind = 12; break;
+        case AZG_NET_TLP4: kind = 13; break;
+        case AZG_NET_TLP5: kind = 14; break;
+        default: break;
+    }
+    if (kind < 0)
+        return fail("azg_forest_async_rounds_mb1d_h2: geometry must be AZG_NET_SPLENDOR3, AZG_NET_SPLENDOR4, AZG_NET_AZUL, AZG_NET_MINIVILLES2 / 3 / 4 or "
+                    "AZG_NET_TLP3 / 4 / 5");
     return async_rounds_impl("azg_forest_async_rounds_mb1d_h2", kind, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, w, descale, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }
@@ -1240,8 +1332,11 @@ extern "C" int azg_forest_async_rounds_hashnet(azg_forest* f, uint8_t* leaf_vali
     (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
     const int kind = game == AZG_SPLENDOR ? (variant == 2 ? 0 : variant == 3 ? 2 : variant == 4 ? 3 : -1)
                      : game == AZG_SANTORINI ? (variant == 1 ? 1 : -1) : game == AZG_AZUL ? 4
-                     : game == AZG_SMALLWORLD ? (variant >= 2 && variant <= 4 ? variant + 4 : -1) : -1;
-    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for Splendor 2 - 4 players, Santorini without gods, Azul and Smallworld 2 - 4 players");
+                     : game == AZG_SMALLWORLD ? (variant >= 2 && variant <= 4 ? variant + 4 : -1)
+                     : game == AZG_MINIVILLES ? (variant >= 2 && variant <= 4 ? variant + 7 : -1)
+                     : game == AZG_TLP ? (variant >= 3 && variant <= 5 ? variant + 9 : -1) : -1;
+    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for Splendor 2 - 4 players, Santorini without gods, Azul, "
+                              "Smallworld 2 - 4 players, Minivilles 2 - 4 players and The Little Prince 3 - 5 players");
     return async_rounds_impl("azg_forest_async_rounds_hashnet", kind, 1, f, leaf_valid, needs_eval, pi, v, noise_stride, nullptr, nullptr, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }

@@ -145,12 +145,20 @@ class SelfPlayEngine:
         sw = gid == _lib.SMALLWORLD and var in (2, 3, 4) and self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_sw62')
         can_sw = sw and (all(type(n).__name__ == 'SmallworldV62Hip' and torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game)
                              for n in nets) or all(getattr(n, 'async_hashnet', False) for n in nets))
+        # ... and, OPT-IN as well, for the two STOCHASTIC games with engine nets: Minivilles 2 - 4 players (V82) and The Little Prince 3 - 5 players
+        # (V83) + MobileNet1dHip(h2=True, fused) of the matching geometry with static output buffers, or the tests' hash-net (the descent draws
+        # the dice / market refills from the tree's own stream exactly as the two-kernel rounds do: DESIGN.md 3.6)
+        geo_st = {(_lib.MINIVILLES, 2): 4, (_lib.MINIVILLES, 3): 6, (_lib.MINIVILLES, 4): 7, (_lib.TLP, 3): 5, (_lib.TLP, 4): 8, (_lib.TLP, 5): 9}.get((gid, var))
+        can_st = (geo_st is not None and self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_mb1d_h2') and
+                  (all(type(n).__name__ == 'MobileNet1dHip' and getattr(n, 'h2', False) and getattr(n, 'fused', False) and
+                       getattr(n, 'geometry', None) == geo_st and torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game)
+                       for n in nets) or all(getattr(n, 'async_hashnet', False) for n in nets)))
         if async_pipe is None:
             async_pipe = any_pipe and groups == 1 and not percu and os.environ.get('AZG_ASYNC', '1') == '1'
-        elif async_pipe and not ((any_pipe or can_sw) and groups == 1):
+        elif async_pipe and not ((any_pipe or can_sw or can_st) and groups == 1):
             raise ValueError('async_pipe=True needs Splendor 2 players + SplendorV80Hip(h2=True), Santorini no-gods + SantoriniV89Hip(h2=True), Splendor 3 / 4 '
-                             'players / Azul + MobileNet1dHip(h2=True) or Smallworld 2 - 4 players + SmallworldV62Hip evaluators with max_batch == n_games '
-                             '(or the tests\' hash-net), groups == 1')
+                             'players / Azul / Minivilles 2 - 4 players / The Little Prince 3 - 5 players + MobileNet1dHip(h2=True) of the game\'s geometry or '
+                             'Smallworld 2 - 4 players + SmallworldV62Hip evaluators with max_batch == n_games (or the tests\' hash-net), groups == 1')
         self.async_pipe = bool(async_pipe)
         self.adaptive = False
         if work_budget is None:

@@ -211,8 +211,12 @@ int azg_forest_async_rounds_v80_h2(azg_forest* f, uint8_t* leaf_valid_dev, uint8
 int azg_forest_async_rounds_conv5_h2(azg_forest* f, uint8_t* leaf_valid_dev, uint8_t* needs_eval_dev, float* pi_dev, float* v_dev,
                                      int noise_stride, const float* const* w, float descale, int rounds, int n_net, int n_sel,
                                      int batch_wait_ticks, int shared_budget, void* stream);
-/* ... and for Splendor 3 / 4 players and Azul with their MobileNet-1d nets: geometry, w (43 device pointers) and descale (16 host floats) as
-   for azg_nn_mb1d_forward_h2; 8 (Splendor) / 16 (Azul) leaves per forward. */
+/* ... and for Splendor 3 / 4 players, Azul, Minivilles 2 - 4 players and The Little Prince 3 - 5 players with their MobileNet-1d nets: geometry
+   (AZG_NET_SPLENDOR3 / 4, AZG_NET_AZUL, AZG_NET_MINIVILLES2 / 3 / 4, AZG_NET_TLP3 / 4 / 5), w (43 device pointers) and descale (16 host floats) as
+   for azg_nn_mb1d_forward_h2; 8 (Splendor, TLP 3 players) / 16 (Azul, Minivilles) / 6 (TLP 4 / 5 players) leaves per forward.  A geometry that
+   is not the forest's game and player count is an error that names both; nothing is launched.  Minivilles and TLP are STOCHASTIC (dice,
+   market refills): the descent draws them from the tree's own counter stream in the order of the two-kernel rounds, so per-tree results
+   are identical bit for bit to those rounds here as well (shared_budget == 0).  Opt-in from Python (SelfPlayEngine(async_pipe=True)). */
 int azg_forest_async_rounds_mb1d_h2(azg_forest* f, int geometry, uint8_t* leaf_valid_dev, uint8_t* needs_eval_dev, float* pi_dev, float* v_dev,
                                     int noise_stride, const void* const* w, const float* descale_host, int rounds, int n_net, int n_sel,
                                     int batch_wait_ticks, int shared_budget, void* stream);

@@ -24,7 +24,8 @@ int azg_eval_hashnet(const int8_t* boards, const uint8_t* valid, int T, int S, i
 /* tests: the ASYNCHRONOUS TREE PIPELINE (include/azg.h azg_forest_async_rounds_v80_h2) with that hash-net as its evaluator instead of an
    engine net -- the persistent descent kernel of the forest's game + a persistent evaluator kernel, same queues, same in-kernel advance --
    so that the pipeline itself can play the oracle's episodes and the episodes the reference's Coach.executeEpisode played
-   (Coach.py:37-84,117-144).  For Splendor 2 - 4 players, Santorini without gods, Azul and Smallworld 2 - 4 players.  Arguments as for azg_forest_async_rounds_v80_h2
+   (Coach.py:37-84,117-144).  For Splendor 2 - 4 players, Santorini without gods, Azul, Smallworld 2 - 4 players, Minivilles 2 - 4 players and
+   The Little Prince 3 - 5 players (any other forest: an error, nothing is launched).  Arguments as for azg_forest_async_rounds_v80_h2
    without the weights.  Not a product path. */
 int azg_forest_async_rounds_hashnet(azg_forest* f, uint8_t* leaf_valid_dev, uint8_t* needs_eval_dev, float* pi_dev, float* v_dev, int noise_stride,
                                     int rounds, int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream);

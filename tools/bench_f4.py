@@ -3,6 +3,7 @@ self-play on the engine with the integer hash-net of SURVEY Appendix C.3 as the 
 figure is the env step + tree side of the plugin, `nnet.TorchModuleEvaluator` adds the user's PyTorch-ROCm module on top).
     python tools/bench_f4.py [--games 1024 --sims 200 --plies 12]
     python tools/bench_f4.py --net engine --pipe --only smallworld    (the V62 net on the asynchronous tree pipeline, csrc/azg_async.hip.h)
+    python tools/bench_f4.py --net engine --pipe --only minivilles    (... and the V82 / V83 MobileNet-1d nets of Minivilles / TLP)
 One JSON line per game: plies/s, simulations/s, ms per round, levels per simulation, valid actions per level, engine errors,
 structural validation of the forest afterwards."""
 import argparse
@@ -54,6 +55,10 @@ class MlpNet(torch.nn.Module):
         return torch.log_softmax(pi, dim=1), torch.tanh(self.v(h))
 
 
+# the rows whose engine nets have a kind in the asynchronous tree pipeline (opt-in there: async_pipe=True)
+PIPE_ROWS = ('smallworld', 'smallworld3', 'smallworld4', 'minivilles', 'minivilles3', 'minivilles4', 'thelittleprince', 'tlp4', 'tlp5')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--net', default='hash', choices=['hash', 'hashhip', 'mlp', 'engine', 'torchnet'],
@@ -67,16 +72,17 @@ def main():
     ap.add_argument('--games', type=int, default=1024)
     ap.add_argument('--sims', type=int, default=200)
     ap.add_argument('--plies', type=int, default=40, help='timed ply waves (one wave = `sims` lock-step rounds)')
-    ap.add_argument('--only', default=None)
-    ap.add_argument('--pipe', action='store_true', help='with --net engine: run the Smallworld rows on the asynchronous tree pipeline (async_pipe=True; '
-                                                           'AZG_ASYNC_NNET / AZG_ASYNC_NSEL set the CU split) and report its profile; other rows are skipped')
+    ap.add_argument('--only', default=None, help='rows to run (comma-separated names)')
+    ap.add_argument('--pipe', action='store_true', help='with --net engine: run the Smallworld, Minivilles and The Little Prince rows on the asynchronous '
+                                                           'tree pipeline (async_pipe=True; AZG_ASYNC_NNET / AZG_ASYNC_NSEL set the CU split) and report its '
+                                                           'profile; other rows are skipped')
     ap.add_argument('--cyc', action='store_true', help='cycle breakdown of k_select per tree and launch (a library built with AZG_DEFINES=AZG_CYC_COUNTERS)')
     a = ap.parse_args()
     for name, make, scale, capf in GAMES:
-        if a.only and a.only != name:
+        if a.only and name not in a.only.split(','):
             continue
         pipe = a.pipe and a.net == 'engine'
-        if pipe and not name.startswith('smallworld'):
+        if pipe and name not in PIPE_ROWS:
             continue
         g = make()
         T = max(64, int(a.games * scale))
