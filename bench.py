@@ -13,10 +13,12 @@ Every ply is a full numMCTSSims search (prob_fullMCTS=1).  value
 timed region / seconds, summed over ranks (Coach.py:71: one getNextState = one env step); the simulation-based figure
 (simulations / numMCTSSims / seconds, which also counts the partial plies at the window edges) is printed next to it.
 
-Extra objects on the JSON line: "roofline" (the select+expand+backup kernel, HIP events on the launch stream, algorithmic
-bytes from live engine counters, SURVEY.md §8d formula), "cpu_baseline" (the C oracle + PyTorch-CPU net on the host
-cores, bounded sample, rank 0 at N=1 only) and "secondary" (the north star's second target, Santorini no-gods, same
-engine, shorter window, with its own roofline).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the result line.
+`--full` adds the measurements that take runs of their own, as extra objects on the JSON line: "roofline" and
+"roofline_net" (the select+expand+backup kernel, HIP events on the launch stream, algorithmic bytes from live engine
+counters, SURVEY.md §8d formula; the net kernel), "sustained" / "value_whole_games" (the same workload over whole games),
+"secondary" (the north star's second target, Santorini no-gods, same engine, shorter window, with its own roofline) and
+"cpu_baseline" (the C oracle + PyTorch-CPU net on the host cores, bounded sample, rank 0 at N=1 only).
 
 `--dump-outputs DIR` writes the example records the timed steps produced as DIR/<name>.npy (see dump_arrays), so that two builds can
 be compared output for output on the same arguments.
@@ -551,19 +553,22 @@ def main():
     ap.add_argument('--prob-full', type=float, default=1.0,
                     help='prob_fullMCTS: 1.0 = every ply a full search (the headline metric); 0.25 = the reference default mix of '
                          'full and numMCTSSims//5 searches (main.py), a secondary figure')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline / roofline_net, the whole-games leg, the secondary leg and '
+                         'the CPU baseline (off: set-up, warm-up, the timed steps, --dump-outputs and the result line only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--cpu-procs', type=int, default=0,
                     help='cpu_baseline on this many host cores (independent single-thread processes, summed); 0 = min(64, host '
                          'cores): the count with the highest total on the 256-thread host -- SURVEY.md §8d asks for the host cores, not one')
     ap.add_argument('--cpu-worker', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--roofline-rounds', type=int, default=300)
+    ap.add_argument('--roofline-rounds', type=int, default=300, help='with --full: rounds of the roofline measurement (0 = none)')
     ap.add_argument('--traffic-json', default=None, help='PMC traffic summary of an earlier profiled run (default: the newest profiles/r*_traffic.json)')
     ap.add_argument('--preroll-plies', type=int, default=-1,
                     help='plies played with fast searches before the warm-up (-1 = per-game default, about 3/4 of a game; 0 = start from '
                          'the opening): moves the games to where they end inside a short timed window, so the example gather is not empty')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the Santorini no-gods leg (north star\'s second target)')
-    ap.add_argument('--no-sustained', action='store_true', help='skip the whole-games leg (value_whole_games)')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the Santorini no-gods leg (north star\'s second target)')
+    ap.add_argument('--no-sustained', action='store_true', help='with --full: skip the whole-games leg (value_whole_games)')
     ap.add_argument('--sustained-steps', type=int, default=70, help='timed ply waves of the whole-games leg')
     ap.add_argument('--secondary-steps', type=int, default=0, help='timed ply waves of the secondary leg (0 = max(3, steps // 5))')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -605,7 +610,7 @@ def main():
     T = a.games
     if os.environ.get('AZG_BENCH_FAIL_RANK') and int(os.environ['AZG_BENCH_FAIL_RANK']) == rank:
         raise SystemExit('AZG_BENCH_FAIL_RANK: rank %d dies on purpose (tests/test_gpu_bench_ranks.py)' % rank)
-    r = run_workload(a, a.game, T, a.steps, a.warmup, rank, world, dev, use_dist, dump=bool(a.dump_outputs))
+    r = run_workload(a, a.game, T, a.steps, a.warmup, rank, world, dev, use_dist, roofline=a.full, dump=bool(a.dump_outputs))
     dumped = None
     if r['outputs'] is not None:
         import numpy as np
@@ -657,7 +662,7 @@ def main():
         dist.barrier()
     # ---- sustained: the same workload over WHOLE games (no pre-roll: opening, middle game, endgame, restart), no roofline legs -- the
     # window above times the phase the pre-roll moved the games to; this is the rate a training run sees ----
-    if a.game == 'splendor2' and not a.no_sustained and (a.preroll_plies != 0 or a.steps < 60):
+    if a.full and a.game == 'splendor2' and not a.no_sustained and (a.preroll_plies != 0 or a.steps < 60):
         try:
             r3 = run_workload(a, a.game, T, a.sustained_steps, 10, rank, world, dev, use_dist, roofline=False, preroll_override=0)
             out['value_whole_games'] = r3['value']
@@ -668,7 +673,7 @@ def main():
         except Exception as ex:
             out['sustained'] = dict(error=repr(ex))
     # ---- secondary: the north star's second target (Santorini no-gods), same engine, shorter window, own roofline ----
-    if a.game == 'splendor2' and not a.no_secondary:
+    if a.full and a.game == 'splendor2' and not a.no_secondary:
         try:
             st = a.secondary_steps or max(3, a.steps // 5)
             r2 = run_workload(a, 'santorini1', T, st, max(1, min(a.warmup, 2)), rank, world, dev, use_dist)
@@ -684,7 +689,7 @@ def main():
                                     examples_gathered=r2['examples_gathered'], preroll_plies=r2['preroll_plies'])
         except Exception as ex:                       # the headline line must still be printed
             out['secondary'] = dict(error=repr(ex))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.game in CPU_GAMES:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and a.game in CPU_GAMES:
         # 64 single-thread processes: the count that gives the HIGHEST total on the 256-thread host (measured: 64 processes
         # 393 env-steps/s in total, 128 processes 297 -- they contend for memory bandwidth and the SMT siblings' units)
         procs = a.cpu_procs or max(1, min(64, os.cpu_count() or 1))

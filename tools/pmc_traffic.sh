@@ -3,7 +3,7 @@ set -x
 R=${GRAFT_REPO_ROOT:-/root/repo}; TAG=$1; shift
 O=$R/gpurun_out/traffic_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py --steps 1 --warmup 1 --preroll-plies 0 --no-secondary --no-cpu-baseline --roofline-rounds 100"
+B="python $R/bench.py --full --steps 1 --warmup 1 --preroll-plies 0 --no-secondary --no-cpu-baseline --roofline-rounds 100"
 env "$@" rocprofv3 --pmc FETCH_SIZE -d /tmp/pf_$TAG -o pf -- $B > $O/bench_f.json 2>/dev/null
 env "$@" rocprofv3 --pmc WRITE_SIZE -d /tmp/pw_$TAG -o pw -- $B > /dev/null 2>&1
 cd $R

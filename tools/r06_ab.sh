@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 O=$R/gpurun_out/r06ab; mkdir -p $O
-B="python $R/bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-secondary --no-sustained --roofline-rounds 400 ${BENCH_ARGS:-}"
+B="python $R/bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-secondary --no-sustained --roofline-rounds 400 ${BENCH_ARGS:-}"
 run() { # name, env...
   n=$1; shift
   env "$@" timeout 600 $B > $O/$n.json 2> $O/$n.err

@@ -5,7 +5,7 @@ for spec in "$@"; do
   IFS=: read -r g envs <<< "$spec"
   args=(X=1); tag=$g
   if [ -n "$envs" ]; then IFS=, read -ra ev <<< "$envs"; args+=("${ev[@]}"); tag=${g}_$(echo $envs | tr -c 'A-Za-z0-9\n' '_'); fi
-  env "${args[@]}" python bench.py --game $g --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-secondary --no-sustained --roofline-rounds 200 2>$O/$tag.err | tail -1 > $O/$tag.json
+  env "${args[@]}" python bench.py --full --game $g --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-secondary --no-sustained --roofline-rounds 200 2>$O/$tag.err | tail -1 > $O/$tag.json
   python - <<PY
 import json
 try:
