@@ -838,9 +838,67 @@ __global__ __launch_bounds__(768) void k_async_net(const AsyncArgs* args) {
 #endif  // AZG_ASYNC_PART_NET
 }  // namespace azg
 
+// THE PIPELINE'S KINDS.  One row per (forest, engine net) the pipeline runs; a kind is a row's number, and everything that depends on the kind
+// is generated from this list or found in it by searching: the descent launcher table (azg_async_sel.hip, which expands the game column only:
+// it must not name the net types), the table ASYNC_KINDS with the net launchers, and the entry points' look-ups and refusal texts
+// (azg_async.hip).  Adding a kind is one row here (and a net policy struct if the net family is new: DESIGN.md 3.6).
+// Columns: the device game type; the net policy; game id and variant of the forest it serves (-1: any variant); its name; what a refusal of
+// another forest says (nullptr: "the geometry does not match the forest's game", with both named); the weight table the net reads; the
+// default split of the CUs -- the net's share in 256ths, and whether the descent side is then grown until no workgroup owns more than 128
+// trees --; the AZG_NET_* geometry of azg_forest_async_rounds_mb1d_h2 the row answers to.
+// Santorini with gods has a descent kernel but no engine net (the hash-net only), and only in builds with AZG_ASYNC_SANTORINI11.  Its row is
+// the LAST one, so that no other kind's number depends on the flag: a build that gave the flag to one translation unit only refuses that
+// kind (the descent launcher's table ends before it, or the look-ups never find it) instead of launching another game's kernel.
+// Default splits.  V80: measured at 4096 x 800 (round 6, descent 19.9 us: see DESIGN.md 3.6); V89: round 5 a forward of 8
+// leaves cost ~75 us of a CU, a descent ~33 us of a sixteenth of one: 13 / 16 for the net (208 + 48 -> 28.8 k env-steps/s, 216 + 40
+// 24.5 k, 204 + 52 28.7 k, 200 + 56 28.3 k; two kernels 26.5 k); round 6 with the forward at 63-70 us (nn_tid): 3 / 4 (208 + 48 -> 26.8 k,
+// 200 + 56 30.5 k, 192 + 64 32.4 k, 184 + 72 31.7 k, 176 + 80 30.7 k; with the claim path off scratch 192 + 64 33.2 k, 196 + 60 33.9 k,
+// 200 + 56 33.6 k: 49 / 64); Splendor 3 / 4 players (forward 55-59 us per 8 leaves, descent 27 us):
+// round 5 25 / 32 for the net (4 players: 200 + 56 -> 35.8 k, 208 + 48 33.1 k, 192 + 64 34.6 k), round 6 with the descent at 22 us
+// 13 / 16 (200 + 56 -> 38.8 k, 208 + 48 40.1 k, 216 + 40 36.1 k); Azul (descent-heavy, forward 29 us per 16):
+// round 5 3 / 8 (96 + 160 -> 70.4 k; 112 + 144 68.6 k, 88 + 168 66.3 k), round 6 13 / 32 (96 + 160 69.9 k, 104 + 152 72.3 k).
+// Smallworld + V62 (forward of 4 / 3 / 2 leaves 157 / 128 / 122 us, descent 36-48 us; DESIGN.md 3.6): 7 / 8 for the net, and never fewer
+// descent workgroups than the 128 trees each can own need.  Measured at 200 simulations, 2 players x 1024 games: 240 + 16 -> 16.7 k plies/s
+// (descent-bound: the waves 94 % busy, trees wait 24 us for one), 224 + 32 24.8 k, 208 + 48 25.4 k; 3 / 4 players x 512: 224 + 32 +4 / +6 %
+// over 240 + 16.
+// Minivilles / TLP + MobileNet-1d (forward of 16 / 8 leaves 23 / 35 us, descent 17-18 / 28-33 us): 1 / 2 and 5 / 8 for the net, with the
+// 128-tree rule (n_net is further capped at ceil(T / leaves per forward)).  Measured at 200 simulations (plies/s, net + descent CUs; profiles/
+// r08_stochastic_pipeline.md): Minivilles 2 players x 1024 games 16 + 240 -> 54.0 k, 32 + 224 104.4 k, 48 + 208 104.8 k, 64 + 192 109.5 k (two
+// kernels 77.4 k); x 4096 games 64 + 192 212 k, 96 + 160 308 k, 128 + 128 363 k, 160 + 96 293 k, 192 + 64 199 k (two kernels 238 k).  TLP 3
+// players x 1024: 32 + 224 35.0 k, 64 + 192 69.4 k, 96 + 160 76.2 k, 128 + 128 75.7 k (two kernels 71.1 k); x 4096: 96 + 160 108 k, 128 + 128
+// 144 k, 160 + 96 173 k, 192 + 64 139 k (two kernels 171 k).
+// The hash-net costs next to nothing: a sixteenth, whatever the kind.
+#ifndef AZG_MV_NET_SHARE_256
+#define AZG_MV_NET_SHARE_256 128            /* default net share of the CUs for Minivilles 2 - 4 players + V82, in 256ths */
+#endif
+#ifndef AZG_TLP_NET_SHARE_256
+#define AZG_TLP_NET_SHARE_256 160           /* default net share of the CUs for The Little Prince 3 - 5 players + V83, in 256ths */
+#endif
+#ifdef AZG_ASYNC_SANTORINI11
+#define AZG_ASYNC_KIND_SANTORINI11(X) X(SantoriniDev<11>, NetNone, AZG_SANTORINI, 11, "Santorini with gods", "Santorini with gods only", WT_C5, 196, false, ASYNC_NO_GEOMETRY)
+#else
+#define AZG_ASYNC_KIND_SANTORINI11(X)
+#endif
+#define AZG_ASYNC_KINDS(X) \
+    X(SplendorDev<2>, NetV80, AZG_SPLENDOR, 2, "Splendor 2 players", "Splendor 2 players only (the V80 geometry of nn_v80_h2.hip.h)", WT_V80, AZG_V80_NET_SHARE_256, false, ASYNC_NO_GEOMETRY)  \
+    X(SantoriniDev<1>, NetC5, AZG_SANTORINI, 1, "Santorini without gods", "Santorini without gods only (the V89 geometry of nn_conv5x5.hip.h)", WT_C5, 196, false, ASYNC_NO_GEOMETRY)           \
+    X(SplendorDev<3>, NetSpl3, AZG_SPLENDOR, 3, "Splendor 3 players", nullptr, WT_MB, 208, false, AZG_NET_SPLENDOR3)                                                                            \
+    X(SplendorDev<4>, NetSpl4, AZG_SPLENDOR, 4, "Splendor 4 players", nullptr, WT_MB, 208, false, AZG_NET_SPLENDOR4)                                                                            \
+    X(AzulDev, NetAzul, AZG_AZUL, -1, "Azul", nullptr, WT_MB, 104, false, AZG_NET_AZUL)                                                                                                         \
+    X(SmallworldDev<2>, NetSw62<2>, AZG_SMALLWORLD, 2, "Smallworld 2 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", WT_SW, 224, true, ASYNC_NO_GEOMETRY)                \
+    X(SmallworldDev<3>, NetSw62<3>, AZG_SMALLWORLD, 3, "Smallworld 3 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", WT_SW, 224, true, ASYNC_NO_GEOMETRY)                \
+    X(SmallworldDev<4>, NetSw62<4>, AZG_SMALLWORLD, 4, "Smallworld 4 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", WT_SW, 224, true, ASYNC_NO_GEOMETRY)                \
+    X(MinivillesDev<2>, NetMv<2>, AZG_MINIVILLES, 2, "Minivilles 2 players", nullptr, WT_MB, AZG_MV_NET_SHARE_256, true, AZG_NET_MINIVILLES2)                                                   \
+    X(MinivillesDev<3>, NetMv<3>, AZG_MINIVILLES, 3, "Minivilles 3 players", nullptr, WT_MB, AZG_MV_NET_SHARE_256, true, AZG_NET_MINIVILLES3)                                                   \
+    X(MinivillesDev<4>, NetMv<4>, AZG_MINIVILLES, 4, "Minivilles 4 players", nullptr, WT_MB, AZG_MV_NET_SHARE_256, true, AZG_NET_MINIVILLES4)                                                   \
+    X(TLPDev<3>, NetTlp<3>, AZG_TLP, 3, "The Little Prince 3 players", nullptr, WT_MB, AZG_TLP_NET_SHARE_256, true, AZG_NET_TLP3)                                                               \
+    X(TLPDev<4>, NetTlp<4>, AZG_TLP, 4, "The Little Prince 4 players", nullptr, WT_MB, AZG_TLP_NET_SHARE_256, true, AZG_NET_TLP4)                                                               \
+    X(TLPDev<5>, NetTlp<5>, AZG_TLP, 5, "The Little Prince 5 players", nullptr, WT_MB, AZG_TLP_NET_SHARE_256, true, AZG_NET_TLP5)                                                               \
+    AZG_ASYNC_KIND_SANTORINI11(X)
+
 #ifdef AZG_ASYNC_PART_SELECT
-// the descent kernel's launcher, called by azg_forest_async_rounds_v80_h2 (azg_async.hip): the two kernels live in two translation units
-// because they want different code generation (build.py)
+// the descent kernel's launcher, called by async_rounds_impl (azg_async.hip) with a row number of AZG_ASYNC_KINDS: the two kernels live in two
+// translation units because they want different code generation (build.py)
 template <class G>
 static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
     static_assert(azg::ASYNC_SEL_WAVES * azg::RoundLds<G>::STRIDE + sizeof(azg::AsyncSelLds) <= 160 * 1024, "the descent workgroup's LDS fits the CU");
@@ -855,35 +913,13 @@ static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStrea
     HIPCHK(hipGetLastError());
     return 0;
 }
-// net_kind: 0 = Splendor 2 players (V80), 1 = Santorini no-gods (V89), 2 / 3 = Splendor 3 / 4 players, 4 = Azul (MobileNet-1d), 5 = Santorini with gods,
-// 6 / 7 / 8 = Smallworld 2 / 3 / 4 players (V62), 9 / 10 / 11 = Minivilles 2 / 3 / 4 players, 12 / 13 / 14 = The Little Prince 3 / 4 / 5 players
-// (MobileNet-1d; the first STOCHASTIC games here: the descent draws their dice / market refills from the tree's stream)
 int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
-#ifdef AZG_ASYNC_ONLY_KIND      /* code-generation experiments: one game's kernel only */
-    if (net_kind != AZG_ASYNC_ONLY_KIND) return -1;
-    return async_launch_select<AZG_ASYNC_ONLY_GAME>(devbuf, n_sel, s);
-#else
-    switch (net_kind) {
-        case 0: return async_launch_select<azg::SplendorDev<2>>(devbuf, n_sel, s);
-        case 1: return async_launch_select<azg::SantoriniDev<1>>(devbuf, n_sel, s);
-        case 2: return async_launch_select<azg::SplendorDev<3>>(devbuf, n_sel, s);
-        case 3: return async_launch_select<azg::SplendorDev<4>>(devbuf, n_sel, s);
-        case 4: return async_launch_select<azg::AzulDev>(devbuf, n_sel, s);
-#ifdef AZG_ASYNC_SANTORINI11
-        case 5: return async_launch_select<azg::SantoriniDev<11>>(devbuf, n_sel, s);
-#endif
-        case 6: return async_launch_select<azg::SmallworldDev<2>>(devbuf, n_sel, s);
-        case 7: return async_launch_select<azg::SmallworldDev<3>>(devbuf, n_sel, s);
-        case 8: return async_launch_select<azg::SmallworldDev<4>>(devbuf, n_sel, s);
-        case 9: return async_launch_select<azg::MinivillesDev<2>>(devbuf, n_sel, s);
-        case 10: return async_launch_select<azg::MinivillesDev<3>>(devbuf, n_sel, s);
-        case 11: return async_launch_select<azg::MinivillesDev<4>>(devbuf, n_sel, s);
-        case 12: return async_launch_select<azg::TLPDev<3>>(devbuf, n_sel, s);
-        case 13: return async_launch_select<azg::TLPDev<4>>(devbuf, n_sel, s);
-        case 14: return async_launch_select<azg::TLPDev<5>>(devbuf, n_sel, s);
-        default: return -1;
-    }
-#endif
+    using Launch = int (*)(const azg::AsyncArgs*, int, hipStream_t);
+#define X(G, ...) &async_launch_select<azg::G>,
+    static const Launch launch[] = {AZG_ASYNC_KINDS(X)};
+#undef X
+    if (net_kind < 0 || net_kind >= (int)(sizeof(launch) / sizeof(launch[0]))) return -1;
+    return launch[net_kind](devbuf, n_sel, s);
 }
 #endif  // AZG_ASYNC_PART_SELECT
 
@@ -897,6 +933,7 @@ struct AsyncSlot {
     int n_sel, n_net, ring_bits;
     int device, n_cu, leaf_stride, T;          // what the buffers were sized for (checked on every reuse)
 };
+constexpr const char* ASYNC_SLOT_KEY = "async_pipeline";   // what the forest keeps the slot under (azg_forest_attach)
 static void async_slot_free(void* p) {
     AsyncSlot* s = (AsyncSlot*)p;
     (void)hipFree(s->devbuf); (void)hipFree(s->aleaf); (void)hipFree(s->ctl); (void)hipFree(s->ring); (void)hipFree(s->ready);
@@ -928,7 +965,7 @@ static AsyncDevice g_async_dev[ASYNC_MAX_DEVICES];
 extern "C" int azg_forest_async_profile(azg_forest* f, double* out /* [ASYNC_NPROF] */, int reset) {
     if (!f || !out) return fail("azg_forest_async_profile: null argument");
     for (int i = 0; i < ASYNC_NPROF; i++) out[i] = 0.0;
-    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, "async_v80");
+    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, ASYNC_SLOT_KEY);
     if (!sl) return 0;
     HIPCHK(hipDeviceSynchronize());
     unsigned long long h[ASYNC_NPROF];
@@ -948,7 +985,7 @@ extern "C" int azg_forest_async_profile(azg_forest* f, double* out /* [ASYNC_NPR
 // include/azg.h: per-workgroup placement and load of the pipeline's kernels (debugging / placement studies)
 extern "C" int azg_forest_async_wginfo(azg_forest* f, unsigned long long* out /* host [max_wg][4] */, int max_wg, int reset) {
     if (!f || !out) return fail("azg_forest_async_wginfo: null argument");
-    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, "async_v80");
+    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, ASYNC_SLOT_KEY);
     if (!sl) return 0;
     const int n = sl->n_sel + sl->n_net < max_wg ? sl->n_sel + sl->n_net : max_wg;
     HIPCHK(hipDeviceSynchronize());
@@ -962,7 +999,7 @@ extern "C" int azg_forest_async_wginfo(azg_forest* f, unsigned long long* out /*
 extern "C" int azg_forest_async_debug(azg_forest* f, unsigned long long* out /* host [792 + 104 * 40] */, uint32_t* ready_out /* host [128 * max_wg] or null */, int max_wg,
                                       unsigned long long* ring_out /* host [ring slots] or null */, int max_ring) {
     if (!f || !out) return fail("azg_forest_async_debug: null argument");
-    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, "async_v80");
+    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, ASYNC_SLOT_KEY);
     if (!sl) return 0;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out, sl->wginfo + (size_t)4 * 1024, sizeof(unsigned long long) * (280 + 512 + 104 * 40), hipMemcpyDeviceToHost));
@@ -971,10 +1008,8 @@ extern "C" int azg_forest_async_debug(azg_forest* f, unsigned long long* out /* 
     return sl->ring_bits;
 }
 
-// One launch of the pipeline.  kind = which game's descent kernel (and, hash == 0, which net): 0 Splendor 2 players + V80 (w = 43 pointers,
-// descale = 16 host floats); 1 Santorini no-gods + V89 (w = 14 pointers, descale = 1 host float); 2 / 3 Splendor 3 / 4 players, 4 Azul
-// (MobileNet-1d: 43 pointers + 16 factors); 5 Santorini with gods (hash-net only so far); 6 / 7 / 8 Smallworld 2 / 3 / 4 players + V62 (w = 25
-// pointers, no descale).  hash != 0: the integer hash-net as the evaluator.
+// One launch of the pipeline.  kind = a row of ASYNC_KINDS: which game's descent kernel and, hash == 0, which net with which weight table (w /
+// descale as the row's entry point in include/azg.h takes them).  hash != 0: the integer hash-net as the evaluator.
 // Recovery, first half: in front of the two persistent kernels, every tree that is still owed the evaluation of the leaf it queued in an
 // earlier launch (status ST_WAIT_NN, `evald` clear: that launch ended early) gets its leaf record -- still in the pipeline's leaf array --
 // back on the ring and is flagged `pending`: its descent workgroup starts it as "in the net".  Costs one tiny launch; in the common case
@@ -1007,57 +1042,58 @@ static int async_net_attr() {
     HIPCHK(hipFuncSetAttribute((const void*)k_async_net<NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     return 0;
 }
-// One row per pipeline kind: the forest it serves (variant -1: any), what a refusal of another forest says (nullptr: "the geometry does not
-// match the forest's game" with both named), the leaf record's stride, the samples of a forward, the weight table the net reads, and the
-// default split of the CUs -- the net's share in 256ths, and whether the descent side is then grown until no workgroup owns more than 128
-// trees.  (The kinds are the cases of the two launch switches below and of azg_async_launch_select.)
+// The table of kinds, generated from AZG_ASYNC_KINDS (above): per row the forest it serves, its texts, the leaf record's stride and the samples
+// of a forward (both read off the row's types), the weight table the net reads, the default split of the CUs, the MobileNet-1d geometry it
+// answers to, and its launchers -- the engine net's, the hash-net's, and the net kernel's LDS attribute.
 enum AsyncWt { WT_V80, WT_C5, WT_MB, WT_SW };
-struct AsyncKind { int game, variant; const char* name; const char* only; int leaf_stride, bs, wt, net_256; bool cap_trees; };
+constexpr int ASYNC_NO_GEOMETRY = -1;
+using AsyncNetLaunch = int (*)(const AsyncArgs*, int, hipStream_t);
+struct AsyncKind {
+    int game, variant; const char* name; const char* only; int leaf_stride, bs, wt, net_256; bool cap_trees; int geometry; const char* geometry_name;
+    AsyncNetLaunch launch_net, launch_hashnet; int (*net_attr)();
+};
 static_assert(AsyncLeaf<SplendorDev<2>>::STRIDE == H2_AL_STRIDE && AsyncLeaf<SplendorDev<2>>::MASK_OFF == H2_AL_MASK, "leaf record layout shared with the net kernel");
 static_assert(AsyncLeaf<SantoriniDev<1>>::STRIDE == C5_AL_STRIDE && AsyncLeaf<SantoriniDev<1>>::MASK_OFF == C5_AL_MASK, "leaf record layout shared with the net kernel");
-// Default splits.  V80: measured at 4096 x 800 (round 6, descent 19.9 us: see DESIGN.md 3.6); V89: round 5 a forward of 8
-// leaves cost ~75 us of a CU, a descent ~33 us of a sixteenth of one: 13 / 16 for the net (208 + 48 -> 28.8 k env-steps/s, 216 + 40
-// 24.5 k, 204 + 52 28.7 k, 200 + 56 28.3 k; two kernels 26.5 k); round 6 with the forward at 63-70 us (nn_tid): 3 / 4 (208 + 48 -> 26.8 k,
-// 200 + 56 30.5 k, 192 + 64 32.4 k, 184 + 72 31.7 k, 176 + 80 30.7 k; with the claim path off scratch 192 + 64 33.2 k, 196 + 60 33.9 k,
-// 200 + 56 33.6 k: 49 / 64); Splendor 3 / 4 players (forward 55-59 us per 8 leaves, descent 27 us):
-// round 5 25 / 32 for the net (4 players: 200 + 56 -> 35.8 k, 208 + 48 33.1 k, 192 + 64 34.6 k), round 6 with the descent at 22 us
-// 13 / 16 (200 + 56 -> 38.8 k, 208 + 48 40.1 k, 216 + 40 36.1 k); Azul (descent-heavy, forward 29 us per 16):
-// round 5 3 / 8 (96 + 160 -> 70.4 k; 112 + 144 68.6 k, 88 + 168 66.3 k), round 6 13 / 32 (96 + 160 69.9 k, 104 + 152 72.3 k).
-// Smallworld + V62 (forward of 4 / 3 / 2 leaves 157 / 128 / 122 us, descent 36-48 us; DESIGN.md 3.6): 7 / 8 for the net, and never fewer
-// descent workgroups than the 128 trees each can own need.  Measured at 200 simulations, 2 players x 1024 games: 240 + 16 -> 16.7 k plies/s
-// (descent-bound: the waves 94 % busy, trees wait 24 us for one), 224 + 32 24.8 k, 208 + 48 25.4 k; 3 / 4 players x 512: 224 + 32 +4 / +6 %
-// over 240 + 16.
-// Minivilles / TLP + MobileNet-1d (forward of 16 / 8 leaves 23 / 35 us, descent 17-18 / 28-33 us): 1 / 2 and 5 / 8 for the net, with the
-// 128-tree rule (n_net is further capped at ceil(T / leaves per forward)).  Measured at 200 simulations (plies/s, net + descent CUs; profiles/
-// r08_stochastic_pipeline.md): Minivilles 2 players x 1024 games 16 + 240 -> 54.0 k, 32 + 224 104.4 k, 48 + 208 104.8 k, 64 + 192 109.5 k (two
-// kernels 77.4 k); x 4096 games 64 + 192 212 k, 96 + 160 308 k, 128 + 128 363 k, 160 + 96 293 k, 192 + 64 199 k (two kernels 238 k).  TLP 3
-// players x 1024: 32 + 224 35.0 k, 64 + 192 69.4 k, 96 + 160 76.2 k, 128 + 128 75.7 k (two kernels 71.1 k); x 4096: 96 + 160 108 k, 128 + 128
-// 144 k, 160 + 96 173 k, 192 + 64 139 k (two kernels 171 k).
-// The hash-net costs next to nothing: a sixteenth, whatever the kind.
-#ifndef AZG_MV_NET_SHARE_256
-#define AZG_MV_NET_SHARE_256 128            /* default net share of the CUs for Minivilles 2 - 4 players + V82, in 256ths */
+#ifdef AZG_ASYNC_SANTORINI11
+struct NetNone { static constexpr int BS = 16; };          // a descent kernel without an engine net: the hash-net only
+template <> int async_launch_net<NetNone>(const AsyncArgs*, int, hipStream_t) { return fail("no engine net for this game in the pipeline"); }
+template <> int async_net_attr<NetNone>() { return 0; }
 #endif
-#ifndef AZG_TLP_NET_SHARE_256
-#define AZG_TLP_NET_SHARE_256 160           /* default net share of the CUs for The Little Prince 3 - 5 players + V83, in 256ths */
-#endif
-static const AsyncKind ASYNC_KINDS[] = {
-    {AZG_SPLENDOR, 2, "Splendor 2 players", "Splendor 2 players only (the V80 geometry of nn_v80_h2.hip.h)", H2_AL_STRIDE, NetV80::BS, WT_V80, AZG_V80_NET_SHARE_256, false},
-    {AZG_SANTORINI, 1, "Santorini without gods", "Santorini without gods only (the V89 geometry of nn_conv5x5.hip.h)", C5_AL_STRIDE, NetC5::BS, WT_C5, 196, false},
-    {AZG_SPLENDOR, 3, "Splendor 3 players", nullptr, AsyncLeaf<SplendorDev<3>>::STRIDE, NetSpl3::BS, WT_MB, 208, false},
-    {AZG_SPLENDOR, 4, "Splendor 4 players", nullptr, AsyncLeaf<SplendorDev<4>>::STRIDE, NetSpl4::BS, WT_MB, 208, false},
-    {AZG_AZUL, -1, "Azul", nullptr, AsyncLeaf<AzulDev>::STRIDE, NetAzul::BS, WT_MB, 104, false},
-    {AZG_SANTORINI, 11, "Santorini with gods", "Santorini with gods only", AsyncLeaf<SantoriniDev<11>>::STRIDE, 16, WT_C5, 196, false},
-    {AZG_SMALLWORLD, 2, "Smallworld 2 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<2>>::STRIDE, NetSw62<2>::BS, WT_SW, 224, true},
-    {AZG_SMALLWORLD, 3, "Smallworld 3 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<3>>::STRIDE, NetSw62<3>::BS, WT_SW, 224, true},
-    {AZG_SMALLWORLD, 4, "Smallworld 4 players", "Smallworld only (the V62 geometry of nn_smallworld.hip.h)", AsyncLeaf<SmallworldDev<4>>::STRIDE, NetSw62<4>::BS, WT_SW, 224, true},
-    {AZG_MINIVILLES, 2, "Minivilles 2 players", nullptr, AsyncLeaf<MinivillesDev<2>>::STRIDE, NetMv<2>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
-    {AZG_MINIVILLES, 3, "Minivilles 3 players", nullptr, AsyncLeaf<MinivillesDev<3>>::STRIDE, NetMv<3>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
-    {AZG_MINIVILLES, 4, "Minivilles 4 players", nullptr, AsyncLeaf<MinivillesDev<4>>::STRIDE, NetMv<4>::BS, WT_MB, AZG_MV_NET_SHARE_256, true},
-    {AZG_TLP, 3, "The Little Prince 3 players", nullptr, AsyncLeaf<TLPDev<3>>::STRIDE, NetTlp<3>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
-    {AZG_TLP, 4, "The Little Prince 4 players", nullptr, AsyncLeaf<TLPDev<4>>::STRIDE, NetTlp<4>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
-    {AZG_TLP, 5, "The Little Prince 5 players", nullptr, AsyncLeaf<TLPDev<5>>::STRIDE, NetTlp<5>::BS, WT_MB, AZG_TLP_NET_SHARE_256, true},
-};
+#define X(G, NET, GAME, VARIANT, NAME, ONLY, WT, NET_256, CAP_TREES, GEOMETRY)                                                                  \
+    {GAME, VARIANT, NAME, ONLY, AsyncLeaf<G>::STRIDE, NET::BS, WT, NET_256, CAP_TREES, GEOMETRY, #GEOMETRY, &async_launch_net<NET>, &async_launch_net<NetHash<G>>, &async_net_attr<NET>},
+static const AsyncKind ASYNC_KINDS[] = {AZG_ASYNC_KINDS(X)};
+#undef X
 constexpr int ASYNC_NKINDS = (int)(sizeof(ASYNC_KINDS) / sizeof(ASYNC_KINDS[0]));
+// look-ups (-1: no such row): the row of a forest's (game, variant), of an AZG_NET_* geometry, of a net policy
+static int async_kind_of_game(int game, int variant) {
+    for (int k = 0; k < ASYNC_NKINDS; k++)
+        if (ASYNC_KINDS[k].game == game && (ASYNC_KINDS[k].variant < 0 || ASYNC_KINDS[k].variant == variant)) return k;
+    return -1;
+}
+static int async_kind_of_forest(azg_forest* f) {
+    int game = 0, variant = 0;
+    double alpha = 0.0;
+    (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
+    return async_kind_of_game(game, variant);
+}
+static int async_kind_of_geometry(int geometry) {
+    for (int k = 0; k < ASYNC_NKINDS; k++)
+        if (ASYNC_KINDS[k].geometry != ASYNC_NO_GEOMETRY && ASYNC_KINDS[k].geometry == geometry) return k;
+    return -1;
+}
+template <class NET>
+static int async_kind_of_net() {
+    for (int k = 0; k < ASYNC_NKINDS; k++)
+        if (ASYNC_KINDS[k].launch_net == &async_launch_net<NET>) return k;
+    return -1;
+}
+// "a, b, c": the names of every row (the games the pipeline has descent kernels for) / the geometry names of the MobileNet-1d rows
+static std::string async_kind_list(bool geometries) {
+    std::string out;
+    for (int k = 0; k < ASYNC_NKINDS; k++)
+        if (!geometries || ASYNC_KINDS[k].geometry != ASYNC_NO_GEOMETRY) out += (out.empty() ? "" : ", ") + std::string(geometries ? ASYNC_KINDS[k].geometry_name : ASYNC_KINDS[k].name);
+    return out;
+}
 static std::string async_forest_name(int game, int variant) {
     static const char* const names[] = {"Splendor", "Santorini", "Azul", "Minivilles", "Abalone", "The Little Prince", "Botanik", "Akropolis", "Smallworld"};
     std::string n = game >= 0 && game < (int)(sizeof(names) / sizeof(names[0])) ? names[game] : "game " + std::to_string(game);
@@ -1096,10 +1132,8 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         HIPCHK(hipStreamCreateWithPriority(&b, hipStreamNonBlocking, hi));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
-        if (async_net_attr<NetV80>() || async_net_attr<NetC5>() || async_net_attr<NetSpl3>() || async_net_attr<NetSpl4>() || async_net_attr<NetAzul>() ||
-            async_net_attr<NetSw62<2>>() || async_net_attr<NetSw62<3>>() || async_net_attr<NetSw62<4>>() || async_net_attr<NetMv<2>>() ||
-            async_net_attr<NetMv<3>>() || async_net_attr<NetMv<4>>() || async_net_attr<NetTlp<3>>() || async_net_attr<NetTlp<4>>() || async_net_attr<NetTlp<5>>())
-            return -1;
+        for (int k = 0; k < ASYNC_NKINDS; k++)
+            if (ASYNC_KINDS[k].net_attr()) return -1;
         D.net_stream = a; D.sel_stream = b; D.n_cu = prop.multiProcessorCount;
     }
     const int n_cu = D.n_cu;
@@ -1116,7 +1150,7 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         return fail(me + ": n_net + n_sel exceeds the CUs of the device (every workgroup of the pipeline must be resident)");
     if ((long long)n_sel * ASYNC_RS < T) return fail(me + ": more than 128 trees per select workgroup");
     if (T >= (1 << 20)) return fail(me + ": at most 2^20 - 1 trees");
-    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, "async_v80");
+    AsyncSlot* sl = (AsyncSlot*)azg_forest_attached(f, ASYNC_SLOT_KEY);
     if (sl && (sl->device != device || sl->n_cu != n_cu || sl->leaf_stride != leaf_stride || sl->T != T))
         return fail(me + ": the forest's pipeline buffers were made for another device / leaf layout (one game and one GPU per forest)");
     if (!sl) {
@@ -1148,7 +1182,7 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
             return fail(me + ": could not allocate the pipeline's queues (" + hipGetErrorString(e) + ")");
         }
         sl = n;
-        azg_forest_attach(f, "async_v80", sl, async_slot_free);
+        azg_forest_attach(f, ASYNC_SLOT_KEY, sl, async_slot_free);
     }
     sl->n_sel = n_sel; sl->n_net = n_net;
     AsyncArgs want;
@@ -1217,48 +1251,7 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
     HIPCHK(hipEventRecord(sl->fork, s));
     HIPCHK(hipStreamWaitEvent(D.net_stream, sl->fork, 0));
     HIPCHK(hipStreamWaitEvent(D.sel_stream, sl->fork, 0));
-    int rc;
-    if (hash) {
-        switch (kind) {
-            case 0: rc = async_launch_net<NetHash<SplendorDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 1: rc = async_launch_net<NetHash<SantoriniDev<1>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 2: rc = async_launch_net<NetHash<SplendorDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 3: rc = async_launch_net<NetHash<SplendorDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 4: rc = async_launch_net<NetHash<AzulDev>>(sl->devbuf, n_net, D.net_stream); break;
-            case 6: rc = async_launch_net<NetHash<SmallworldDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 7: rc = async_launch_net<NetHash<SmallworldDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 8: rc = async_launch_net<NetHash<SmallworldDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 9: rc = async_launch_net<NetHash<MinivillesDev<2>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 10: rc = async_launch_net<NetHash<MinivillesDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 11: rc = async_launch_net<NetHash<MinivillesDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 12: rc = async_launch_net<NetHash<TLPDev<3>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 13: rc = async_launch_net<NetHash<TLPDev<4>>>(sl->devbuf, n_net, D.net_stream); break;
-            case 14: rc = async_launch_net<NetHash<TLPDev<5>>>(sl->devbuf, n_net, D.net_stream); break;
-#ifdef AZG_ASYNC_SANTORINI11
-            case 5: rc = async_launch_net<NetHash<SantoriniDev<11>>>(sl->devbuf, n_net, D.net_stream); break;
-#endif
-            default: return fail(me + ": no descent kernel for this game in the pipeline");
-        }
-    } else {
-        switch (kind) {
-            case 0: rc = async_launch_net<NetV80>(sl->devbuf, n_net, D.net_stream); break;
-            case 1: rc = async_launch_net<NetC5>(sl->devbuf, n_net, D.net_stream); break;
-            case 2: rc = async_launch_net<NetSpl3>(sl->devbuf, n_net, D.net_stream); break;
-            case 3: rc = async_launch_net<NetSpl4>(sl->devbuf, n_net, D.net_stream); break;
-            case 4: rc = async_launch_net<NetAzul>(sl->devbuf, n_net, D.net_stream); break;
-            case 6: rc = async_launch_net<NetSw62<2>>(sl->devbuf, n_net, D.net_stream); break;
-            case 7: rc = async_launch_net<NetSw62<3>>(sl->devbuf, n_net, D.net_stream); break;
-            case 8: rc = async_launch_net<NetSw62<4>>(sl->devbuf, n_net, D.net_stream); break;
-            case 9: rc = async_launch_net<NetMv<2>>(sl->devbuf, n_net, D.net_stream); break;
-            case 10: rc = async_launch_net<NetMv<3>>(sl->devbuf, n_net, D.net_stream); break;
-            case 11: rc = async_launch_net<NetMv<4>>(sl->devbuf, n_net, D.net_stream); break;
-            case 12: rc = async_launch_net<NetTlp<3>>(sl->devbuf, n_net, D.net_stream); break;
-            case 13: rc = async_launch_net<NetTlp<4>>(sl->devbuf, n_net, D.net_stream); break;
-            case 14: rc = async_launch_net<NetTlp<5>>(sl->devbuf, n_net, D.net_stream); break;
-            default: return fail(me + ": no engine net for this game in the pipeline");
-        }
-    }
-    if (rc) return -1;
+    if ((hash ? K.launch_hashnet : K.launch_net)(sl->devbuf, n_net, D.net_stream)) return -1;
     if (azg_async_launch_select(kind, sl->devbuf, n_sel, D.sel_stream)) return -1;
     HIPCHK(hipEventRecord(sl->join_net, D.net_stream));
     HIPCHK(hipEventRecord(sl->join, D.sel_stream));
@@ -1275,30 +1268,16 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
 extern "C" int azg_forest_async_rounds_v80_h2(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
                                               const void* const* w, const float* descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                                               int shared_budget, void* stream) {
-    return async_rounds_impl("azg_forest_async_rounds_v80_h2", 0, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, w, descale, rounds, n_net, n_sel,
-                             batch_wait_ticks, shared_budget, stream);
+    return async_rounds_impl("azg_forest_async_rounds_v80_h2", async_kind_of_net<NetV80>(), 0, f, leaf_valid, needs_eval, pi, v, noise_stride, w, descale, rounds,
+                             n_net, n_sel, batch_wait_ticks, shared_budget, stream);
 }
 // include/azg.h: the pipeline for Splendor 3 / 4 players, Azul, Minivilles 2 - 4 players and The Little Prince 3 - 5 players with their MobileNet-1d
 // nets (geometry = AZG_NET_* of azg_nn_mb1d_forward_h2)
 extern "C" int azg_forest_async_rounds_mb1d_h2(azg_forest* f, int geometry, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
                                                const void* const* w, const float* descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                                                int shared_budget, void* stream) {
-    int kind = -1;
-    switch (geometry) {
-        case AZG_NET_SPLENDOR3: kind = 2; break;
-        case AZG_NET_SPLENDOR4: kind = 3; break;
-        case AZG_NET_AZUL: kind = 4; break;
-        case AZG_NET_MINIVILLES2: kind = 9; break;
-        case AZG_NET_MINIVILLES3: kind = 10; break;
-        case AZG_NET_MINIVILLES4: kind = 11; break;
-        case AZG_NET_TLP3: kind = 12; break;
-        case AZG_NET_TLP4: kind = 13; break;
-        case AZG_NET_TLP5: kind = 14; break;
-        default: break;
-    }
-    if (kind < 0)
-        return fail("azg_forest_async_rounds_mb1d_h2: geometry must be AZG_NET_SPLENDOR3, AZG_NET_SPLENDOR4, AZG_NET_AZUL, AZG_NET_MINIVILLES2 / 3 / 4 or "
-                    "AZG_NET_TLP3 / 4 / 5");
+    const int kind = async_kind_of_geometry(geometry);
+    if (kind < 0) return fail("azg_forest_async_rounds_mb1d_h2: geometry must be one of " + async_kind_list(true));
     return async_rounds_impl("azg_forest_async_rounds_mb1d_h2", kind, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, w, descale, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }
@@ -1306,8 +1285,8 @@ extern "C" int azg_forest_async_rounds_mb1d_h2(azg_forest* f, int geometry, uint
 extern "C" int azg_forest_async_rounds_conv5_h2(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
                                                 const float* const* w, float descale, int rounds, int n_net, int n_sel, int batch_wait_ticks,
                                                 int shared_budget, void* stream) {
-    return async_rounds_impl("azg_forest_async_rounds_conv5_h2", 1, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, (const void* const*)w, &descale, rounds,
-                             n_net, n_sel, batch_wait_ticks, shared_budget, stream);
+    return async_rounds_impl("azg_forest_async_rounds_conv5_h2", async_kind_of_net<NetC5>(), 0, f, leaf_valid, needs_eval, pi, v, noise_stride,
+                             (const void* const*)w, &descale, rounds, n_net, n_sel, batch_wait_ticks, shared_budget, stream);
 }
 
 // include/azg.h: the pipeline for a Smallworld forest (2 / 3 / 4 players, read from the forest) with the V62 net (the 25 pointers of
@@ -1315,28 +1294,18 @@ extern "C" int azg_forest_async_rounds_conv5_h2(azg_forest* f, uint8_t* leaf_val
 extern "C" int azg_forest_async_rounds_sw62(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride,
                                             const float* const* w, int rounds, int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream) {
     if (!f) return fail("azg_forest_async_rounds_sw62: null argument");
-    int game = 0, variant = 0;
-    double alpha = 0.0;
-    (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
-    if (game != AZG_SMALLWORLD || variant < 2 || variant > 4) return fail("azg_forest_async_rounds_sw62: Smallworld 2 - 4 players only (the V62 geometry of nn_smallworld.hip.h)");
-    return async_rounds_impl("azg_forest_async_rounds_sw62", variant + 4, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, (const void* const*)w, nullptr,
-                             rounds, n_net, n_sel, batch_wait_ticks, shared_budget, stream);
+    const int kind = async_kind_of_forest(f);
+    if (kind < 0 || ASYNC_KINDS[kind].wt != WT_SW) return fail(std::string("azg_forest_async_rounds_sw62: ") + ASYNC_KINDS[async_kind_of_net<NetSw62<2>>()].only);
+    return async_rounds_impl("azg_forest_async_rounds_sw62", kind, 0, f, leaf_valid, needs_eval, pi, v, noise_stride, (const void* const*)w, nullptr, rounds,
+                             n_net, n_sel, batch_wait_ticks, shared_budget, stream);
 }
 
 // include/azg_testaids.h: the pipeline with the integer hash-net as its evaluator, for every game that has a descent kernel here
 extern "C" int azg_forest_async_rounds_hashnet(azg_forest* f, uint8_t* leaf_valid, uint8_t* needs_eval, float* pi, float* v, int noise_stride, int rounds,
                                                int n_net, int n_sel, int batch_wait_ticks, int shared_budget, void* stream) {
     if (!f) return fail("azg_forest_async_rounds_hashnet: null argument");
-    int game = 0, variant = 0;
-    double alpha = 0.0;
-    (void)azg_forest_dev_internal(f, &game, &variant, &alpha);
-    const int kind = game == AZG_SPLENDOR ? (variant == 2 ? 0 : variant == 3 ? 2 : variant == 4 ? 3 : -1)
-                     : game == AZG_SANTORINI ? (variant == 1 ? 1 : -1) : game == AZG_AZUL ? 4
-                     : game == AZG_SMALLWORLD ? (variant >= 2 && variant <= 4 ? variant + 4 : -1)
-                     : game == AZG_MINIVILLES ? (variant >= 2 && variant <= 4 ? variant + 7 : -1)
-                     : game == AZG_TLP ? (variant >= 3 && variant <= 5 ? variant + 9 : -1) : -1;
-    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for Splendor 2 - 4 players, Santorini without gods, Azul, "
-                              "Smallworld 2 - 4 players, Minivilles 2 - 4 players and The Little Prince 3 - 5 players");
+    const int kind = async_kind_of_forest(f);
+    if (kind < 0) return fail("azg_forest_async_rounds_hashnet: the pipeline has descent kernels for " + async_kind_list(false));
     return async_rounds_impl("azg_forest_async_rounds_hashnet", kind, 1, f, leaf_valid, needs_eval, pi, v, noise_stride, nullptr, nullptr, rounds, n_net, n_sel,
                              batch_wait_ticks, shared_budget, stream);
 }

@@ -1,4 +1,5 @@
 """Thin Python handle on an `azg_forest` (include/azg.h).  torch is used only for device buffers and streams."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,65 @@ def _ptr(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---- the asynchronous tree pipeline's table (the C++ side is AZG_ASYNC_KINDS in csrc/azg_async.hip.h) ----
+# A net family: how an evaluator is recognised and how its C entry point is called -- entry(forest, *head(net), leaf_valid, needs_eval, pi, v,
+# noise, *weights(net), rounds, n_net, n_sel, batch_wait_ticks, shared_budget, stream).
+PipelineNet = collections.namedtuple('PipelineNet', 'name match entry head weights')
+
+
+def _by_class(cls, *flags):
+    return lambda n: type(n).__name__ == cls and all(getattr(n, f, False) for f in flags)
+
+
+NET_HASH = PipelineNet("the tests' hash-net", lambda n: bool(getattr(n, 'async_hashnet', False)),      # (tests/hashnet.py HashNetPipeline, include/azg_testaids.h)
+                       'azg_forest_async_rounds_hashnet', lambda n: (), lambda n: ())
+NET_V80 = PipelineNet('SplendorV80Hip(h2=True)', lambda n: bool(getattr(n, 'h2', False) and getattr(n, 'fused_net', False) and hasattr(n, 'net_ptrs_h2')),
+                      'azg_forest_async_rounds_v80_h2', lambda n: (), lambda n: (n.net_ptrs_h2, n.descale_h2))         # 43 pointers + 16 descale factors
+NET_V89 = PipelineNet('SantoriniV89Hip(h2=True)', _by_class('SantoriniV89Hip', 'h2'),
+                      'azg_forest_async_rounds_conv5_h2', lambda n: (), lambda n: (n.ptrs, float(n.descale)))           # 14 pointers + the trunk's descale
+NET_MB1D = PipelineNet("MobileNet1dHip(h2=True) of the game's geometry", _by_class('MobileNet1dHip', 'h2', 'fused'),
+                       'azg_forest_async_rounds_mb1d_h2', lambda n: (int(n.geometry),), lambda n: (n.fused_ptrs_h2, n.descale_h2))
+NET_SW62 = PipelineNet('SmallworldV62Hip', _by_class('SmallworldV62Hip'),
+                       'azg_forest_async_rounds_sw62', lambda n: (), lambda n: (n.ptrs,))                                # the 25 pointers of azg_nn_sw62_forward
+PIPELINE_NETS = (NET_HASH, NET_MB1D, NET_SW62, NET_V89, NET_V80)
+
+# A row: the forests it serves (variants None: any), the engine net's family, the AZG_NET_* geometry (include/azg.h) the net must have (by
+# variant where it differs), and whether SelfPlayEngine takes the pipeline by default or only with async_pipe=True (the default stays the two-kernel rounds
+# until the numbers decide otherwise).  Every row also runs with the tests' hash-net.
+PipelineRow = collections.namedtuple('PipelineRow', 'name game variants net geometry default_on')
+PIPELINE_ROWS = (
+    PipelineRow('Splendor 2 players', _lib.SPLENDOR, (0, 2), NET_V80, None, True),           # (variant 0 = the game's default: 2 players)
+    PipelineRow('Santorini no-gods', _lib.SANTORINI, (1,), NET_V89, None, True),
+    PipelineRow('Splendor 3 / 4 players', _lib.SPLENDOR, (3, 4), NET_MB1D, {3: 1, 4: 2}, True),
+    PipelineRow('Azul', _lib.AZUL, None, NET_MB1D, 3, True),
+    PipelineRow('Smallworld 2 - 4 players', _lib.SMALLWORLD, (2, 3, 4), NET_SW62, None, False),
+    PipelineRow('Minivilles 2 - 4 players', _lib.MINIVILLES, (2, 3, 4), NET_MB1D, {2: 4, 3: 6, 4: 7}, False),
+    PipelineRow('The Little Prince 3 - 5 players', _lib.TLP, (3, 4, 5), NET_MB1D, {3: 5, 4: 8, 5: 9}, False),
+)
+
+
+def pipeline_row(game_id, variant, fused, nets, trees, A):
+    """The row of PIPELINE_ROWS that runs this engine on the pipeline, or None: the game and variant are the row's, the rounds are the
+    fused ones, and the evaluators (one per group) are all the hash-net or all the row's engine net, of the row's geometry, with static
+    output buffers pi of (trees per group, A)."""
+    var = int(variant or 0)
+    for row in PIPELINE_ROWS:
+        if not fused or row.game != game_id or (row.variants is not None and var not in row.variants):
+            continue
+        geo = row.geometry.get(var) if isinstance(row.geometry, dict) else row.geometry
+        if all(NET_HASH.match(n) for n in nets) or all(
+                row.net.match(n) and (geo is None or getattr(n, 'geometry', None) == geo) and
+                torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (trees, A) for n in nets):
+            return row
+    return None
+
+
+def pipeline_needs():
+    """what async_pipe=True needs, for the refusal"""
+    return 'async_pipe=True needs %s evaluators with max_batch == n_games (or the tests\' hash-net), groups == 1' % ', '.join(
+        '%s + %s' % (r.name, r.net.name) for r in PIPELINE_ROWS)
 
 
 class Forest:
@@ -120,36 +180,20 @@ class Forest:
         check(lib().azg_forest_rounds_v80_h2(self.h, _ptr(self.leaf_states), _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
                                              -2 if device_noise else 0, net.net_ptrs_h2, net.descale_h2, int(rounds), _stream()))
 
-    def async_rounds_v80(self, net, pi, v, rounds, device_noise=False, n_net=0, n_sel=0, batch_wait_ticks=-1, shared_budget=False):
-        """`rounds` (descent, forward) pairs per tree as ONE launch of the asynchronous pipeline (azg_forest_async_rounds_v80_h2): persistent
-        descent workgroups and persistent V80 net workgroups resident together, leaves and trees handed over through device-side queues"""
+    def async_rounds(self, net, pi, v, rounds, device_noise=False, n_net=0, n_sel=0, batch_wait_ticks=-1, shared_budget=False):
+        """`rounds` (descent, forward) pairs per tree as ONE launch of the asynchronous pipeline (the azg_forest_async_rounds_* entry point of
+        the evaluator's family, PIPELINE_NETS): persistent descent workgroups and persistent net workgroups resident together, leaves and
+        trees handed over through device-side queues"""
         assert pi.dtype == torch.float32 and v.dtype == torch.float32 and pi.is_contiguous() and v.is_contiguous()
         assert pi.shape == (self.T, self.A) and v.shape == (self.T, self.P)
-        if getattr(net, 'async_hashnet', False):        # the tests' integer hash-net as the pipeline's evaluator (include/azg_testaids.h)
-            check(lib().azg_forest_async_rounds_hashnet(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
-                                                        -2 if device_noise else 0, int(rounds), int(n_net), int(n_sel), int(batch_wait_ticks),
-                                                        int(bool(shared_budget)), _stream()))
-            return
-        if hasattr(net, 'fused_ptrs_h2'):               # the MobileNet-1d family (MobileNet1dHip: 43 pointers + 16 descale factors + geometry)
-            check(lib().azg_forest_async_rounds_mb1d_h2(self.h, int(net.geometry), _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
-                                                        -2 if device_noise else 0, net.fused_ptrs_h2, net.descale_h2, int(rounds), int(n_net), int(n_sel),
-                                                        int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
-            return
-        if self.cfg.game == _lib.SMALLWORLD:           # the V62 transformer (SmallworldV62Hip: the 25 pointers of azg_nn_sw62_forward)
-            if type(net).__name__ != 'SmallworldV62Hip':
-                raise ValueError('the Smallworld pipeline evaluates SmallworldV62Hip (the engine kernel), not %s' % type(net).__name__)
-            check(lib().azg_forest_async_rounds_sw62(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
-                                                     -2 if device_noise else 0, net.ptrs, int(rounds), int(n_net), int(n_sel),
-                                                     int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
-            return
-        if self.cfg.game == _lib.SANTORINI:            # the V89 net (SantoriniV89Hip: 14 pointers + the trunk's descale)
-            check(lib().azg_forest_async_rounds_conv5_h2(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
-                                                         -2 if device_noise else 0, net.ptrs, float(net.descale), int(rounds), int(n_net), int(n_sel),
-                                                         int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
-            return
-        check(lib().azg_forest_async_rounds_v80_h2(self.h, _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
-                                                   -2 if device_noise else 0, net.net_ptrs_h2, net.descale_h2, int(rounds), int(n_net), int(n_sel),
-                                                   int(batch_wait_ticks), int(bool(shared_budget)), _stream()))
+        fam = next((f for f in PIPELINE_NETS if f.match(net)), None)
+        if fam is None:
+            raise ValueError('the pipeline evaluates %s, not %s' % (' / '.join(f.name for f in PIPELINE_NETS), type(net).__name__))
+        check(getattr(lib(), fam.entry)(self.h, *fam.head(net), _ptr(self.leaf_valid), _ptr(self.needs_eval), _ptr(pi), _ptr(v),
+                                        -2 if device_noise else 0, *fam.weights(net), int(rounds), int(n_net), int(n_sel), int(batch_wait_ticks),
+                                        int(bool(shared_budget)), _stream()))
+
+    async_rounds_v80 = async_rounds                  # (the name from when the V80 net was the only one)
 
     def async_counters(self, reset=False):
         """the pipeline's raw counters (include/azg.h azg_forest_async_profile: 96 numbers, accumulated since the last reset)"""

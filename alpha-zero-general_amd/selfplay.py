@@ -26,7 +26,7 @@ import ctypes as C
 
 import torch
 
-from .forest import Forest
+from .forest import NET_V80, Forest, pipeline_needs, pipeline_row
 
 
 class _Group:
@@ -61,10 +61,10 @@ class _Group:
     def rounds(self, n, fused, percu, advance=True):
         """n lock-step rounds of this group's trees on the current stream, then (advance) one selfplay_advance.  percu: ONE launch of
         the per-CU round kernel (azg_forest_rounds_v80_h2: 16 trees + their 16 leaves per workgroup, no launch boundary between rounds);
-        percu == 'async': ONE launch of the asynchronous pipeline (azg_forest_async_rounds_v80_h2: n descent / forward pairs per tree)"""
+        percu == 'async': ONE launch of the asynchronous pipeline (Forest.async_rounds: n descent / forward pairs per tree)"""
         if percu == 'async':
             # (no selfplay_advance: in the pipeline a tree whose search is finished advances at once, on the wave that found it finished)
-            self.f.async_rounds_v80(self.net, self.pi, self.v, n, device_noise=bool(self.device_noise), **self.async_cfg)
+            self.f.async_rounds(self.net, self.pi, self.v, n, device_noise=bool(self.device_noise), **self.async_cfg)
             return
         if percu:
             self.f.rounds_v80(self.net, self.pi, self.v, n, device_noise=bool(self.device_noise))
@@ -108,12 +108,14 @@ class SelfPlayEngine:
         splendor = getattr(game, 'GAME_ID', None) == _lib.SPLENDOR
         Tg = n_games // groups
         nets = nnet if isinstance(nnet, (list, tuple)) else [nnet] + [nnet.clone_buffers() for _ in range(groups - 1)]
-        # the per-CU round kernel and the asynchronous pipeline exist for Splendor 2 players + the V80 net on its f16 x 2 kernel with static
-        # output buffers
-        A_game = _lib.game_info(game.GAME_ID, game.variant)[1]
-        can = (splendor and int(getattr(game, 'variant', 0) or 2) == 2 and self.fused and
-               all(getattr(n, 'h2', False) and getattr(n, 'fused_net', False) and hasattr(n, 'net_ptrs_h2') and
-                   torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game) for n in nets))
+        # the asynchronous tree pipeline (csrc/azg_async.hip.h): persistent descent + net workgroups, no launch-wide boundary between the
+        # descents and the forwards; round 5: 100 k env-steps/s against 79 k for the two-kernel rounds at 4096 x 800.  Which games and
+        # evaluators it runs, and which of them by default, is forest.PIPELINE_ROWS; one group.  AZG_ASYNC=0 / async_pipe=False: the
+        # two-kernel rounds.
+        row = pipeline_row(getattr(game, 'GAME_ID', None), getattr(game, 'variant', 0), self.fused, nets, Tg,
+                           _lib.game_info(game.GAME_ID, game.variant)[1])
+        # the per-CU round kernel exists for Splendor 2 players + the V80 net on its f16 x 2 kernel with static output buffers
+        can = row is not None and row.net is NET_V80 and all(NET_V80.match(n) for n in nets)
         if percu is None:
             # opt-in (AZG_PERCU=1 / percu=True): measured on one MI355X at 4096 x 800 it is the slower form of the round (65.1 k against
             # 72.5 k env-steps/s, DESIGN.md 3.6: the 16-wave / 128-VGPR net phase costs 40 us against 32 for the 12-wave kernel and the
@@ -121,44 +123,10 @@ class SelfPlayEngine:
             percu = can and os.environ.get('AZG_PERCU', '0') == '1'
         elif percu and not can:
             raise ValueError('percu=True needs Splendor 2 players and SplendorV80Hip(h2=True) evaluators with max_batch == games per group')
-        # the asynchronous tree pipeline (csrc/azg_async.hip.h): persistent descent + net workgroups, no launch-wide boundary between the
-        # descents and the forwards; round 5: 100 k env-steps/s against 79 k for the two-kernel rounds at 4096 x 800.  Same preconditions
-        # as the per-CU kernel, one group.  AZG_ASYNC=0 / async_pipe=False: the two-kernel rounds.
-        # ... and for Santorini without gods + the V89 net on its f16 x 2 kernel (SantoriniV89Hip(h2=True)) with static output buffers
-        can_c5 = (getattr(game, 'GAME_ID', None) == _lib.SANTORINI and int(getattr(game, 'variant', 0) or 0) == 1 and self.fused and
-                  hasattr(_lib.lib(), 'azg_forest_async_rounds_conv5_h2') and
-                  all(type(n).__name__ == 'SantoriniV89Hip' and getattr(n, 'h2', False) and torch.is_tensor(getattr(n, 'pi', None)) and
-                      tuple(n.pi.shape) == (Tg, A_game) for n in nets))
-        # ... and for Splendor 3 / 4 players and Azul + their MobileNet-1d nets on the f16 x 2 one-launch kernel (MobileNet1dHip(h2=True, fused))
-        gid, var = getattr(game, 'GAME_ID', None), int(getattr(game, 'variant', 0) or 0)
-        can_mb = (self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_mb1d_h2') and
-                  ((gid == _lib.SPLENDOR and var in (3, 4)) or gid == _lib.AZUL) and
-                  all(type(n).__name__ == 'MobileNet1dHip' and getattr(n, 'h2', False) and getattr(n, 'fused', False) and
-                      getattr(n, 'geometry', None) == ({3: 1, 4: 2}.get(var) if gid == _lib.SPLENDOR else 3) and
-                      torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game) for n in nets))
-        # ... and, for the parity tests, with the integer hash-net as the evaluator (tests/hashnet.py HashNetPipeline: async_hashnet = True)
-        can_hash = (self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_hashnet') and all(getattr(n, 'async_hashnet', False) for n in nets) and
-                    ((gid == _lib.SPLENDOR and var in (0, 2, 3, 4)) or (gid == _lib.SANTORINI and var == 1) or gid == _lib.AZUL))
-        any_pipe = can or can_c5 or can_mb or can_hash
-        # ... and, OPT-IN only (async_pipe=True; the default stays the two-kernel rounds until the numbers decide otherwise), for
-        # Smallworld 2 - 4 players + the V62 transformer on its one-launch kernel (SmallworldV62Hip) with static output buffers, or the tests' hash-net
-        sw = gid == _lib.SMALLWORLD and var in (2, 3, 4) and self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_sw62')
-        can_sw = sw and (all(type(n).__name__ == 'SmallworldV62Hip' and torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game)
-                             for n in nets) or all(getattr(n, 'async_hashnet', False) for n in nets))
-        # ... and, OPT-IN as well, for the two STOCHASTIC games with engine nets: Minivilles 2 - 4 players (V82) and The Little Prince 3 - 5 players
-        # (V83) + MobileNet1dHip(h2=True, fused) of the matching geometry with static output buffers, or the tests' hash-net (the descent draws
-        # the dice / market refills from the tree's own stream exactly as the two-kernel rounds do: DESIGN.md 3.6)
-        geo_st = {(_lib.MINIVILLES, 2): 4, (_lib.MINIVILLES, 3): 6, (_lib.MINIVILLES, 4): 7, (_lib.TLP, 3): 5, (_lib.TLP, 4): 8, (_lib.TLP, 5): 9}.get((gid, var))
-        can_st = (geo_st is not None and self.fused and hasattr(_lib.lib(), 'azg_forest_async_rounds_mb1d_h2') and
-                  (all(type(n).__name__ == 'MobileNet1dHip' and getattr(n, 'h2', False) and getattr(n, 'fused', False) and
-                       getattr(n, 'geometry', None) == geo_st and torch.is_tensor(getattr(n, 'pi', None)) and tuple(n.pi.shape) == (Tg, A_game)
-                       for n in nets) or all(getattr(n, 'async_hashnet', False) for n in nets)))
         if async_pipe is None:
-            async_pipe = any_pipe and groups == 1 and not percu and os.environ.get('AZG_ASYNC', '1') == '1'
-        elif async_pipe and not ((any_pipe or can_sw or can_st) and groups == 1):
-            raise ValueError('async_pipe=True needs Splendor 2 players + SplendorV80Hip(h2=True), Santorini no-gods + SantoriniV89Hip(h2=True), Splendor 3 / 4 '
-                             'players / Azul / Minivilles 2 - 4 players / The Little Prince 3 - 5 players + MobileNet1dHip(h2=True) of the game\'s geometry or '
-                             'Smallworld 2 - 4 players + SmallworldV62Hip evaluators with max_batch == n_games (or the tests\' hash-net), groups == 1')
+            async_pipe = row is not None and row.default_on and groups == 1 and not percu and os.environ.get('AZG_ASYNC', '1') == '1'
+        elif async_pipe and not (row is not None and groups == 1):
+            raise ValueError(pipeline_needs())
         self.async_pipe = bool(async_pipe)
         self.adaptive = False
         if work_budget is None:
