@@ -10,10 +10,64 @@ with `azg_amd.mcts.MCTS`-based players already works unchanged (one game at a ti
     argmax is the most visited action (first index on ties, np.argmax); once temp_for_game(turn) <= 0.02 (late in long games)
     getActionProb itself returns a one-hot on a maximum drawn at random among ties (MCTS.py:93-98; the tree's counter RNG);
   * the real move uses random_seed = 0 (Arena.py:84) -- the engine's counter-based RNG stream of that game;
-  * the result of a game is getGameEnded(board, curPlayer)[0] (Arena.py:101), tallied like playGames (:126-131)."""
+  * the result of a game is getGameEnded(board, curPlayer)[0] (Arena.py:101), tallied like playGames (:126-131).
+
+Baselines (pit.py's players, <G>Players.py): instead of an nnet a contestant may be a RandomContestant() -- <G>Players.RandomPlayer.play,
+uniform among the valid moves -- or a PolicyContestant(nnet) -- the net's policy without a search.  Neither owns a forest; their move
+is one launch of azg_pick_actions (csrc/pick.hip.h) on the [T, A] rows of the ply.  vs_random(...) is the pit-style call."""
+import ctypes as C
+
 import torch
 
+from ._lib import check, lib
+from .games import _ptr, _stream
 from .mcts import BatchedMCTS
+
+PICK_UNIFORM, PICK_ARGMAX, PICK_SAMPLE = 0, 1, 2
+
+
+def pick_actions(mode, probs, valid, active=None, rng_seed=0, stream0=0, counters=None, out=None):
+    """azg_pick_actions (include/azg.h) on CUDA tensors: one action per row of probs f32[T, A] / valid u8[T, A] (either may be None where
+    the mode allows it).  mode 0: uniform among the valid actions; 1: first-index argmax of probs over them; 2: sampled proportionally to
+    probs over them.  Modes 0 and 2 draw from (rng_seed, stream0 + row, counters[row]) and advance counters (int64[T]) by one.  Rows with
+    active == 0 keep what `out` (int32[T], zeros when not given) holds and their counter.  -> out"""
+    ref = probs if probs is not None else valid
+    assert ref is not None, 'pick_actions needs probs or valid for the shape of the rows'
+    T, A = ref.shape
+    for x, dt in ((probs, (torch.float32,)), (valid, (torch.uint8, torch.bool)), (active, (torch.uint8, torch.bool))):
+        assert x is None or (x.dtype in dt and x.is_contiguous() and x.device == ref.device), 'pick_actions: dtype / layout of an argument'
+    assert (probs is None or valid is None or probs.shape == valid.shape) and (active is None or active.shape == (T,))
+    assert counters is None or (counters.dtype == torch.int64 and counters.shape == (T,) and counters.is_contiguous())
+    if out is None:
+        out = torch.zeros(T, dtype=torch.int32, device=ref.device)
+    assert out.dtype == torch.int32 and out.shape == (T,) and out.is_contiguous()
+    check(lib().azg_pick_actions(int(mode), _ptr(probs), _ptr(valid), T, A, _ptr(active), C.c_uint64(int(rng_seed) & (2 ** 64 - 1)),
+                                 C.c_uint64(int(stream0) & (2 ** 64 - 1)), _ptr(counters), _ptr(out), _stream()))
+    return out
+
+
+class RandomContestant:
+    """<G>Players.RandomPlayer.play as an arena contestant: uniform among getValidMoves(canonical, 0)"""
+    mode = PICK_UNIFORM
+
+    def probs_valid(self, game, canonical):
+        return None, game.valid_moves_batch(canonical, None)
+
+
+class PolicyContestant:
+    """the raw policy of `nnet` as an arena contestant: one predict_batch per ply (all T rows of the wave: a fixed batch shape, rows of
+    games where the contestant is not to move are ignored), then the first-index argmax over the valid moves, or with sample=True a move
+    drawn proportionally to the policy (np.random.choice(A, p=pi))"""
+
+    def __init__(self, nnet, sample=False):
+        if not hasattr(nnet, 'predict_batch'):
+            raise TypeError('PolicyContestant needs a net with predict_batch(boards, valids)')
+        self.nnet, self.mode = nnet, PICK_SAMPLE if sample else PICK_ARGMAX
+
+    def probs_valid(self, game, canonical):
+        valid = game.valid_moves_batch(canonical, None)
+        pi, _ = self.nnet.predict_batch(canonical.view((canonical.shape[0],) + tuple(game.getBoardSize())), valid.bool())
+        return pi.float().contiguous(), valid
 
 
 class BatchedArena:
@@ -25,8 +79,11 @@ class BatchedArena:
         self.game, self.T, self.stream0 = game, n_parallel, stream0
         self.temp_for_game = temp_for_game
         kw = [dict(rng_seed=int(getattr(game, 'rng_seed', 0)), stream0=stream0 + (c + 1) * (1 << 30) + first_game_index) for c in (0, 1)]
-        self.mcts = [BatchedMCTS(game, nnet1, args1, n_parallel, node_capacity=node_capacity, **kw[0]),
-                     BatchedMCTS(game, nnet2, args2 if args2 is not None else args1, n_parallel, node_capacity=node_capacity, **kw[1])]
+        # a contestant is a search (BatchedMCTS on its own forest) or a baseline object; self.mcts lists the searches only
+        self.contestants = [n if isinstance(n, (RandomContestant, PolicyContestant)) else
+                            BatchedMCTS(game, n, a, n_parallel, node_capacity=node_capacity, **kw[c])
+                            for c, (n, a) in enumerate(((nnet1, args1), (nnet2, args2 if args2 is not None else args1)))]
+        self.mcts = [m for m in self.contestants if isinstance(m, BatchedMCTS)]
         self.max_plies = 4096
 
     def play_wave(self, first_game_index=0, n_games=None, record=None):
@@ -44,6 +101,9 @@ class BatchedArena:
         zero_seed = torch.zeros(T, dtype=torch.int64, device=dev)
         for m in self.mcts:
             m.reset_all_search_trees()                                       # Arena.py:99
+        # a baseline contestant draws game i's moves from a stream of its own, stream0 + (c + 1) << 30 + i, from counter 0: a function of the
+        # game index only, whatever n_parallel and however the match is dealt out
+        pick_counters = [None if isinstance(m, BatchedMCTS) else torch.zeros(T, dtype=torch.int64, device=dev) for m in self.contestants]
         for ply in range(self.max_plies):
             if bool(done.all().item()):
                 break
@@ -51,9 +111,14 @@ class BatchedArena:
             owner = torch.where((cur == 0) == one_vs_two, torch.zeros_like(cur), torch.ones_like(cur))
             canonical = g.canonical_batch(boards, cur)
             actions = torch.zeros(T, dtype=torch.int32, device=dev)
-            for c, m in enumerate(self.mcts):
+            for c, m in enumerate(self.contestants):
                 active = (~done) & (owner == c)
                 if not bool(active.any().item()):
+                    continue
+                if pick_counters[c] is not None:
+                    probs, valid = m.probs_valid(g, canonical)
+                    pick_actions(m.mode, probs, valid, active, rng_seed=int(getattr(g, 'rng_seed', 0)),
+                                 stream0=self.stream0 + (c + 1) * (1 << 30) + first_game_index, counters=pick_counters[c], out=actions)
                     continue
                 full = torch.where(active, torch.ones(T, dtype=torch.uint8, device=dev), torch.full((T,), 2, dtype=torch.uint8, device=dev))
                 temp = 1 if self.temp_for_game is None else self.temp_for_game(ply + 1)       # `it` of Arena.py:67-68
@@ -87,3 +152,10 @@ class BatchedArena:
             two += int(((ovt & win_other) | (~ovt & win_first_seat)).sum().item())
             draws += int((~(win_first_seat | win_other)).sum().item())
         return one, two, draws
+
+
+def vs_random(game, nnet, args, num, **kw):
+    """pit.py's first question of a net: `num` games of (nnet, args) with its search against RandomContestant, seats alternating as in
+    playGames -> (won, lost, draws) from the net's side.  kw: BatchedArena's (n_parallel defaults to min(num, 64))"""
+    kw.setdefault('n_parallel', max(1, min(int(num), 64)))
+    return BatchedArena(game, nnet, RandomContestant(), args, **kw).playGames(num)

@@ -21,6 +21,7 @@
 #include "game_akropolis.hip.h"
 #include "game_smallworld.hip.h"
 #include "selfplay.hip.h"
+#include "pick.hip.h"
 #include "azg_host.h"
 
 using namespace azg;
@@ -168,6 +169,39 @@ extern "C" int azg_env_symmetries(int game, int variant, const int8_t* states, c
                                   int max_sym, int8_t* out_states, float* out_pi, uint8_t* out_valids, int32_t* out_count,
                                   void* stream) {
     return azg_env_symmetries_ex(game, variant, states, pi, valids, n, max_sym, out_states, out_pi, out_valids, out_count, 0, 0, stream);
+}
+
+// ---- one move per game without a search (pick.hip.h) -------------------------------------------------------------------
+extern "C" int azg_pick_actions(int mode, const float* probs, const uint8_t* valid, int T, int A, const uint8_t* active,
+                                uint64_t rng_seed, uint64_t stream0, uint64_t* counters, int32_t* actions_out, void* stream) {
+    if (mode != AZG_PICK_UNIFORM && mode != AZG_PICK_ARGMAX && mode != AZG_PICK_SAMPLE) return fail("azg_pick_actions: mode must be 0, 1 or 2");
+    if (T == 0) return 0;
+    if (mode != AZG_PICK_UNIFORM && !probs) return fail("azg_pick_actions: modes 1 and 2 need probs");
+    if (T < 0 || A <= 0 || !actions_out) return fail("azg_pick_actions: bad argument");
+    const dim3 grid(T), block(64);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == AZG_PICK_UNIFORM) k_pick_actions<AZG_PICK_UNIFORM><<<grid, block, 0, s>>>(probs, valid, T, A, active, rng_seed, stream0, counters, actions_out);
+    else if (mode == AZG_PICK_ARGMAX) k_pick_actions<AZG_PICK_ARGMAX><<<grid, block, 0, s>>>(probs, valid, T, A, active, rng_seed, stream0, counters, actions_out);
+    else k_pick_actions<AZG_PICK_SAMPLE><<<grid, block, 0, s>>>(probs, valid, T, A, active, rng_seed, stream0, counters, actions_out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// test aid (azg_testaids.h): the uniforms of the RNG contract as the device generator draws them
+__global__ __launch_bounds__(64) void k_debug_rng_u01(uint64_t rng_seed, uint64_t stream0, uint64_t counter0, int n_streams, int n_counters, double* out) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (i >= (size_t)n_streams * (size_t)n_counters) return;
+    Rng rng{rng_seed, stream0 + i / (size_t)n_counters, counter0 + i % (size_t)n_counters};
+    out[i] = rng.u01();
+}
+extern "C" int azg_debug_rng_u01(uint64_t rng_seed, uint64_t stream0, uint64_t counter0, int n_streams, int n_counters, double* out_dev, void* stream) {
+    if (n_streams < 0 || n_counters < 0 || !out_dev) return fail("azg_debug_rng_u01: bad argument");
+    const size_t n = (size_t)n_streams * (size_t)n_counters;
+    if (n == 0) return 0;
+    if (n > (size_t)1 << 30) return fail("azg_debug_rng_u01: too many draws");
+    k_debug_rng_u01<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, (hipStream_t)stream>>>(rng_seed, stream0, counter0, n_streams, n_counters, out_dev);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 // debugging aid: leave a known pattern in the LDS of every CU and in the scratch (private) memory of the queue, so that a kernel that reads

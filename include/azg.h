@@ -87,6 +87,20 @@ int azg_env_symmetries_ex(int game, int variant, const int8_t* states_dev, const
                           int max_sym, int8_t* out_states_dev, float* out_pi_dev, uint8_t* out_valids_dev,
                           int32_t* out_count_dev, uint64_t rng_seed, uint64_t stream0, void* stream);
 
+/* ---- one move per game without a search (one wavefront per game) ----------------------------------------------------
+   Replaces <G>Players.RandomPlayer.play (mode 0), np.argmax of a policy or of getActionProb's vector (mode 1: Arena.py:79, pit.py's
+   raw-policy players) and np.random.choice(A, p=pi) (mode 2) for T games at once.  probs_dev f32[T][A] (modes 1, 2), valid_dev u8[T][A]
+   as azg_env_valid_moves writes it (NULL = every action valid), active_dev u8[T] (NULL = every game): a game with active == 0 keeps its
+   actions_out_dev[t] and its counters_dev[t].
+     mode 0: u = RNG contract (rng_seed, stream0 + t, counters_dev[t]); the floor(u nv)-th of the nv valid actions in index order.
+     mode 1: the first index of the maximum of probs over the valid actions; a NaN never wins; no candidate -> 0.
+     mode 2: the same u; weights = probs where valid and > 0, else 0; the first index whose cumulative weight (f64, index order) exceeds
+             u * total; when rounding leaves none (or the total is 0), the last valid index.
+   Modes 0 and 2 advance counters_dev[t] by exactly one, also when the game has no valid action (the action is then 0);
+   counters_dev == NULL draws at counter 0.  T == 0 launches nothing; a bad mode, or NULL probs in modes 1 and 2, is an error. */
+int azg_pick_actions(int mode, const float* probs_dev, const uint8_t* valid_dev, int T, int A, const uint8_t* active_dev,
+                     uint64_t rng_seed, uint64_t stream0, uint64_t* counters_dev, int32_t* actions_out_dev, void* stream);
+
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */
 typedef struct azg_forest_cfg {

@@ -42,6 +42,11 @@ int azg_forest_async_wginfo(azg_forest* f, unsigned long long* out_host, int max
    null): the leaf ring.  Returns the ring's log2 size (0: the forest never ran the pipeline). */
 int azg_forest_async_debug(azg_forest* f, unsigned long long* out792_host, uint32_t* ready_out_host, int max_wg, unsigned long long* ring_out_host, int max_ring);
 
+/* tests: the uniforms of the RNG contract (include/azg.h) as the engine's device generator draws them:
+   out_dev f64[n_streams][n_counters], out[i][j] = u01(rng_seed, stream0 + i, counter0 + j).  Lets a test state what a kernel must do with
+   a draw without restating the generator. */
+int azg_debug_rng_u01(uint64_t rng_seed, uint64_t stream0, uint64_t counter0, int n_streams, int n_counters, double* out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
