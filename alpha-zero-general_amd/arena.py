@@ -14,7 +14,9 @@ with `azg_amd.mcts.MCTS`-based players already works unchanged (one game at a ti
 
 Baselines (pit.py's players, <G>Players.py): instead of an nnet a contestant may be a RandomContestant() -- <G>Players.RandomPlayer.play,
 uniform among the valid moves -- or a PolicyContestant(nnet) -- the net's policy without a search.  Neither owns a forest; their move
-is one launch of azg_pick_actions (csrc/pick.hip.h) on the [T, A] rows of the ply.  vs_random(...) is the pit-style call."""
+is one launch of azg_pick_actions (csrc/pick.hip.h) on the [T, A] rows of the ply.  vs_random(...) is the pit-style call.
+nnet.RolloutEvaluator in the place of an nnet makes a contestant a pure MCTS (uniform prior, random playouts as the leaf value), and
+random_games(...) plays whole random games in one launch (csrc/playout.hip.h)."""
 import ctypes as C
 
 import torch
@@ -159,3 +161,15 @@ def vs_random(game, nnet, args, num, **kw):
     playGames -> (won, lost, draws) from the net's side.  kw: BatchedArena's (n_parallel defaults to min(num, 64))"""
     kw.setdefault('n_parallel', max(1, min(int(num), 64)))
     return BatchedArena(game, nnet, RandomContestant(), args, **kw).playGames(num)
+
+
+def random_games(game, num, stream0=0, max_plies=4096):
+    """`num` games of uniformly random play from Board.init_game to the end, in two launches (launcher.py's random play; BatchedArena with two
+    RandomContestants pays half a dozen launches and a host round trip per ply): init_boards_batch on streams stream0 .. stream0 + num - 1, then
+    one playout per board on the same streams from the counters the init left.  Game i is a function of (game.rng_seed, stream0 + i) alone.
+    -> (ended f32[num, P] = getGameEnded(final board, final player), plies i32[num], status u8[num]: 0 finished, 1 max_plies reached, 2 no
+    valid move; ended is zero for 1 and 2)"""
+    counters = torch.zeros(num, dtype=torch.int64, device=game.device)
+    boards = game.init_boards_batch(num, stream0, counters)
+    out = game.playouts_batch(boards, k=1, max_plies=max_plies, stream0=stream0, counters=counters)
+    return out.ended[:, 0, :], out.plies[:, 0], out.status[:, 0]

@@ -11,15 +11,7 @@
 
 #include "../../include/azg.h"
 #include "../../include/azg_testaids.h"
-#include "game_splendor.hip.h"
-#include "game_santorini.hip.h"
-#include "game_azul.hip.h"
-#include "game_minivilles.hip.h"
-#include "game_abalone.hip.h"
-#include "game_tlp.hip.h"
-#include "game_botanik.hip.h"
-#include "game_akropolis.hip.h"
-#include "game_smallworld.hip.h"
+#include "azg_dispatch.h"
 #include "selfplay.hip.h"
 #include "pick.hip.h"
 #include "azg_host.h"
@@ -35,32 +27,6 @@ extern "C" int azg_forest_cfg_size(void) { return (int)sizeof(azg_forest_cfg); }
 extern "C" int azg_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 extern "C" int azg_set_device(int d) { HIPCHK(hipSetDevice(d)); return 0; }
 
-// ---- game dispatch --------------------------------------------------------------------------------------------------
-#define AZG_DISPATCH(game, variant, ...)                                                         \
-    do {                                                                                           \
-        if ((game) == AZG_SPLENDOR && (variant) == 2) { using G = SplendorDev<2>; __VA_ARGS__; }          \
-        else if ((game) == AZG_SPLENDOR && (variant) == 3) { using G = SplendorDev<3>; __VA_ARGS__; }     \
-        else if ((game) == AZG_SPLENDOR && (variant) == 4) { using G = SplendorDev<4>; __VA_ARGS__; }     \
-        else if ((game) == AZG_SANTORINI && (variant) == 1) { using G = SantoriniDev<1>; __VA_ARGS__; }   \
-        else if ((game) == AZG_SANTORINI && (variant) == 11) { using G = SantoriniDev<11>; __VA_ARGS__; } \
-        else if ((game) == AZG_AZUL) { using G = AzulDev; __VA_ARGS__; }                                   \
-        else if ((game) == AZG_ABALONE) { using G = AbaloneDev; __VA_ARGS__; }                             \
-        else if ((game) == AZG_MINIVILLES && (variant) == 2) { using G = MinivillesDev<2>; __VA_ARGS__; } \
-        else if ((game) == AZG_MINIVILLES && (variant) == 3) { using G = MinivillesDev<3>; __VA_ARGS__; } \
-        else if ((game) == AZG_MINIVILLES && (variant) == 4) { using G = MinivillesDev<4>; __VA_ARGS__; } \
-        else if ((game) == AZG_TLP && (variant) == 3) { using G = TLPDev<3>; __VA_ARGS__; }               \
-        else if ((game) == AZG_TLP && (variant) == 4) { using G = TLPDev<4>; __VA_ARGS__; }               \
-        else if ((game) == AZG_TLP && (variant) == 5) { using G = TLPDev<5>; __VA_ARGS__; }               \
-        else if ((game) == AZG_BOTANIK) { using G = BotanikDev; __VA_ARGS__; }                             \
-        else if ((game) == AZG_AKROPOLIS && (variant) == 2) { using G = AkropolisDev<2>; __VA_ARGS__; }   \
-        else if ((game) == AZG_AKROPOLIS && (variant) == 3) { using G = AkropolisDev<3>; __VA_ARGS__; }   \
-        else if ((game) == AZG_AKROPOLIS && (variant) == 4) { using G = AkropolisDev<4>; __VA_ARGS__; }   \
-        else if ((game) == AZG_SMALLWORLD && (variant) == 2) { using G = SmallworldDev<2>; __VA_ARGS__; } \
-        else if ((game) == AZG_SMALLWORLD && (variant) == 3) { using G = SmallworldDev<3>; __VA_ARGS__; } \
-        else if ((game) == AZG_SMALLWORLD && (variant) == 4) { using G = SmallworldDev<4>; __VA_ARGS__; } \
-        else return fail("unsupported game/variant");                                              \
-    } while (0)
-
 // games whose expanded nodes carry many more entries than the default heap sizing assumes name their typical count (REC_NV_HINT)
 // ... or the AVERAGE record size in bytes over the nodes of a tree (REC_BYTES_HINT, measured), when the default -- room for 64 entries in
 // every record, plus a quarter -- would make the heap twice what the records take (Azul: three nodes in four fit one 32-entry page)
@@ -68,19 +34,6 @@ template <class G, class = void> struct RecBytesHint { static constexpr int valu
 template <class G> struct RecBytesHint<G, std::void_t<decltype(G::REC_BYTES_HINT)>> { static constexpr int value = G::REC_BYTES_HINT; };
 template <class G, class = void> struct RecNvHint { static constexpr int value = 0; };
 template <class G> struct RecNvHint<G, std::void_t<decltype(G::REC_NV_HINT)>> { static constexpr int value = G::REC_NV_HINT; };
-
-static int norm_variant(int game, int variant) {
-    if (game == AZG_SPLENDOR) return variant ? variant : 2;
-    if (game == AZG_SANTORINI) return variant ? variant : 11;
-    if (game == AZG_AZUL) return 2;
-    if (game == AZG_MINIVILLES) return variant ? variant : 2;
-    if (game == AZG_ABALONE) return 1;
-    if (game == AZG_TLP) return variant ? variant : 3;
-    if (game == AZG_BOTANIK) return 2;
-    if (game == AZG_AKROPOLIS) return variant ? variant : 2;
-    if (game == AZG_SMALLWORLD) return variant ? variant : 2;
-    return variant;
-}
 
 extern "C" int azg_game_info(int game, int variant, int* S, int* A, int* P, int* rows, int* cols) {
     variant = norm_variant(game, variant);

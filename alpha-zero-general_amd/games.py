@@ -3,6 +3,7 @@
 Same method names, argument meaning and return types as the reference's adaptors (splendor/SplendorGame.py:16-60,
 santorini/SantoriniGame.py:16-60, Game.py:14-162).  Every method also has a `*_batch` twin that takes and returns
 torch CUDA tensors for n boards at once -- that is the form the engine itself uses."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -18,6 +19,29 @@ def _ptr(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+Playouts = collections.namedtuple('Playouts', 'ended plies status boards players actions')
+
+
+def playouts_into(game, boards, players, k, max_plies, active, stream0, counters, ended, plies, status, out_boards=None, out_players=None,
+                  out_actions=None):
+    """azg_env_playouts (include/azg.h) into tensors the caller owns: k random playouts from each of boards int8[n, S] (players int32[n] or
+    None, active u8 / bool[n] or None, counters int64[n * k] or None) -> ended f32[n, k, P], plies int32[n, k], status u8[n, k] and, where
+    given, out_boards int8[n, k, S], out_players int32[n, k], out_actions int32[n, k, max_plies].  Rows of a board with active == 0 are
+    left as they are.  One launch on the current stream, nothing allocated, nothing synchronised."""
+    n, k, max_plies = boards.shape[0], int(k), int(max_plies)
+    boards = boards.reshape(n, -1)
+    assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.shape[1] == game.S
+    for x, dt, shape in ((players, (torch.int32,), (n,)), (active, (torch.uint8, torch.bool), (n,)), (counters, (torch.int64,), (n * k,)),
+                         (ended, (torch.float32,), (n, k, game.P)), (plies, (torch.int32,), (n, k)), (status, (torch.uint8,), (n, k)),
+                         (out_boards, (torch.int8,), (n, k, game.S)), (out_players, (torch.int32,), (n, k)),
+                         (out_actions, (torch.int32,), (n, k, max_plies))):
+        assert x is None or (x.dtype in dt and tuple(x.shape) == shape and x.is_contiguous() and x.device == boards.device), \
+            'playouts: dtype / shape / layout of an argument'
+    check(lib().azg_env_playouts(game.GAME_ID, game.variant, _ptr(boards), _ptr(players), _ptr(active), n, k, max_plies,
+                                 C.c_uint64(int(game.rng_seed) & (2 ** 64 - 1)), C.c_uint64(int(stream0) & (2 ** 64 - 1)), _ptr(counters),
+                                 _ptr(ended), _ptr(plies), _ptr(status), _ptr(out_boards), _ptr(out_players), _ptr(out_actions), _stream()))
 
 
 class HipGame:
@@ -73,6 +97,24 @@ class HipGame:
         check(lib().azg_env_init_boards(self.GAME_ID, self.variant, n, _ptr(out), self.rng_seed, stream0, _ptr(counters),
                                         _stream()))
         return out
+
+    def playouts_batch(self, boards, players=None, k=1, max_plies=4096, active=None, stream0=0, counters=None, final_boards=False,
+                       trace=False):
+        """k random playouts from each of n boards, each to the end of its game, in one launch (azg_env_playouts): every move uniform among
+        the valid ones, playout j of board t on RNG stream stream0 + t * k + j from counters[t * k + j] (int64[n * k], advanced in place;
+        None: from 0).  -> Playouts(ended f32[n, k, P] in the seat numbering of the input board, plies i32[n, k], status u8[n, k]: 0
+        finished / 1 max_plies reached / 2 no valid move (ended is zero for 1 and 2), boards int8[n, k, S] and players i32[n, k] at the end
+        with final_boards, actions i32[n, k, max_plies] (-1 past plies) with trace).  Rows of a board with active == 0 come back as zeros
+        (actions -1) and keep their counters."""
+        n, dev = boards.shape[0], self.device
+        ended = torch.zeros((n, k, self.P), dtype=torch.float32, device=dev)
+        plies = torch.zeros((n, k), dtype=torch.int32, device=dev)
+        status = torch.zeros((n, k), dtype=torch.uint8, device=dev)
+        ob = torch.zeros((n, k, self.S), dtype=torch.int8, device=dev) if final_boards else None
+        op = torch.zeros((n, k), dtype=torch.int32, device=dev) if final_boards else None
+        oa = torch.full((n, k, max_plies), -1, dtype=torch.int32, device=dev) if trace else None
+        playouts_into(self, boards, players, k, max_plies, active, stream0, counters, ended, plies, status, ob, op, oa)
+        return Playouts(ended, plies, status, ob, op, oa)
 
     def max_symmetries(self):
         return {0: 10 + 2 * self.P, 1: 8, 2: 120, 3: 1, 4: 12, 5: 2 * self.P + 1, 6: 14, 7: 6, 8: 3}[self.GAME_ID]    # Splendor, Santorini, Azul, Minivilles, Abalone, TLP, Botanik, Akropolis, Smallworld

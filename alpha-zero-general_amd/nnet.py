@@ -1564,3 +1564,75 @@ class TorchModuleEvaluator:
 
     def clone_buffers(self):
         return self
+
+
+class RolloutEvaluator:
+    """Leaf evaluator WITHOUT a net -- the pure-MCTS contestant, and the way to search a game that has no checkpoint yet: a uniform prior
+    over the valid moves, and as the value of a leaf the mean result of `n_playouts` uniformly random playouts from it, all of a batch in
+    one launch of azg_env_playouts (csrc/playout.hip.h).  The leaves are canonical (the player to move is seat 0) and the playouts'
+    results are in the seat numbering of the board they start from, so v[t, 0] is the leaf player's own expected result: NeuralNet.predict's
+    v (MCTS.py:131,153,175-178).  Same `predict_batch` contract as the engine nets, so BatchedMCTS / MCTS / BatchedArena / SelfPlayEngine
+    take it wherever they take an nnet (on the two-kernel rounds: it is no pipeline net).
+
+    Playout j of batch row t draws from stream stream0 + t * n_playouts + j at counters[t * n_playouts + j]; the kernel advances the
+    counters, so every call -- a replay of a captured round too -- plays fresh games.  Rows whose `valids` row is empty (the leaf rows a
+    round never wrote) run nothing: pi and v are zero and their counters stay."""
+
+    _BLOCK = 1 << 32                      # streams between an evaluator and its clone_buffers() copies
+
+    def __init__(self, game, n_playouts=8, max_plies=4096, stream0=1 << 40, max_batch=1):
+        if int(n_playouts) < 1 or not 1 <= int(max_plies) <= 65535:
+            raise ValueError('RolloutEvaluator: n_playouts >= 1 and 1 <= max_plies <= 65535')
+        self.game, self.device = game, game.device
+        self.k, self.max_plies, self.stream0 = int(n_playouts), int(max_plies), int(stream0)
+        self.S, self.A, self.P = game.S, game.A, game.P
+        self._family = [int(stream0), 0]  # shared by the clones: the first evaluator's stream0, clones handed out so far
+        self.counters = torch.zeros(0, dtype=torch.int64, device=self.device)
+        self._alloc(max(1, int(max_batch)))
+
+    def _alloc(self, B):
+        dev, k, old = self.device, self.k, self.counters
+        self.maxB = B
+        self.pi = torch.zeros((B, self.A), dtype=torch.float32, device=dev)
+        self.v = torch.zeros((B, self.P), dtype=torch.float32, device=dev)
+        self.ended = torch.zeros((B, k, self.P), dtype=torch.float32, device=dev)
+        self.plies = torch.zeros((B, k), dtype=torch.int32, device=dev)
+        self.status = torch.zeros((B, k), dtype=torch.uint8, device=dev)
+        self.active = torch.zeros(B, dtype=torch.uint8, device=dev)
+        self.counters = torch.zeros(B * k, dtype=torch.int64, device=dev)
+        n = min(old.numel(), B * k)
+        self.counters[:n] = old[:n]       # (a larger batch keeps the streams it already drew from where they are)
+
+    def clone_buffers(self):
+        """an evaluator with its own buffers and counters on a stream block of its own (concurrent groups never share a stream)"""
+        other = copy.copy(self)
+        self._family[1] += 1
+        other.stream0 = self._family[0] + self._family[1] * self._BLOCK
+        other.counters = torch.zeros(0, dtype=torch.int64, device=self.device)
+        other._alloc(self.maxB)
+        return other
+
+    @torch.no_grad()
+    def predict_batch(self, boards, valids):
+        from .games import playouts_into
+        B = boards.shape[0]
+        if B > self.maxB:
+            self._alloc(B)
+        boards = boards.reshape(B, -1)
+        va = valids.to(torch.float32)
+        assert va.shape == (B, self.A) and va.is_cuda
+        cnt = va.sum(dim=1, keepdim=True)
+        pi, v, active = self.pi[:B], self.v[:B], self.active[:B]
+        torch.div(va, cnt.clamp(min=1.0), out=pi)
+        active.copy_(cnt[:, 0] != 0)
+        playouts_into(self.game, boards, None, self.k, self.max_plies, active, self.stream0, self.counters[:B * self.k],
+                      self.ended[:B], self.plies[:B], self.status[:B])
+        torch.mean(self.ended[:B], dim=1, out=v)
+        v.mul_(active[:, None])           # (an idle row's playout results are whatever an earlier call left there)
+        return pi, v
+
+    def predict(self, board, valid_actions):
+        b = torch.as_tensor(np.asarray(board, dtype=np.int8)).reshape(1, -1).to(self.device)
+        va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
+        pi, v = self.predict_batch(b, va)
+        return pi[0].cpu().numpy(), v[0].cpu().numpy()

@@ -101,6 +101,41 @@ int azg_env_symmetries_ex(int game, int variant, const int8_t* states_dev, const
 int azg_pick_actions(int mode, const float* probs_dev, const uint8_t* valid_dev, int T, int A, const uint8_t* active_dev,
                      uint64_t rng_seed, uint64_t stream0, uint64_t* counters_dev, int32_t* actions_out_dev, void* stream);
 
+/* ---- random playouts to the end of the game, one launch (one wavefront per playout) -----------------------------------
+   Replaces <G>Players.RandomPlayer.play looped by Arena.playGame (Arena.py:67-84) and launcher.py's random play: k playouts from each
+   of n states, every move uniform among the valid ones, the state on chip from the first ply to the last.  Row r = t * k + j is
+   playout j of state t and owns the RNG contract's stream (rng_seed, stream0 + r), from counters_dev[r] (NULL: from 0, nothing written
+   back).  A ply, in this order:
+     1. getGameEnded(board, player): any entry non-zero -> the playout is over, status 0;
+     2. plies == max_plies -> status 1 (cap), the result row is all zeros;
+     3. getValidMoves(board, player): none -> status 2, the result row is all zeros;
+     4. one uniform u; the min(floor(u nv), nv - 1)-th of the nv valid actions in index order (azg_pick_actions, mode 0);
+     5. getNextState(board, player, action, random_seed = 0) on the same stream: a game's dice, refills and card draws follow the pick's
+        draw; plies += 1.
+   This is what the ply-by-ply loop azg_env_game_ended / azg_env_valid_moves / azg_pick_actions(mode 0) / azg_env_next_state computes when
+   its pick and its env step share (stream0, counters_dev).  At the end counters_dev[r] holds the stream's next counter.
+   SEAT FRAME: out_ended_dev is in the seat numbering of the INPUT board -- the env step never renumbers seats.  For a canonical leaf
+   (the player to move is seat 0) entry 0 is therefore the result of the player to move, which is what NeuralNet.predict's v[0] means
+   (MCTS.py:131,153,175-178).
+   active_dev u8[n] (NULL = every state): the k rows of a state with active == 0 keep their outputs and their counters.  Optional
+   outputs may be NULL; entries of out_actions_dev past a row's plies are left as they were.  n == 0 launches nothing.  An unknown
+   game / variant, k < 1, max_plies outside 1 .. 65535 or a NULL required output is an error and launches nothing.  No synchronisation
+   and no allocation: the call can sit inside a captured round. */
+int azg_env_playouts(int game, int variant,
+                     const int8_t* states_dev,      /* [n][S] */
+                     const int32_t* players_dev,    /* [n], NULL = player 0 everywhere */
+                     const uint8_t* active_dev,     /* [n], NULL = every row */
+                     int n, int k, int max_plies,
+                     uint64_t rng_seed, uint64_t stream0,
+                     uint64_t* counters_dev,        /* [n*k] or NULL (start at 0, not written back) */
+                     float*   out_ended_dev,        /* [n][k][P]  getGameEnded(final board, final player) */
+                     int32_t* out_plies_dev,        /* [n][k] */
+                     uint8_t* out_status_dev,       /* [n][k]  0 finished, 1 cap, 2 no valid move */
+                     int8_t*  out_states_dev,       /* [n][k][S] or NULL: the final boards */
+                     int32_t* out_players_dev,      /* [n][k] or NULL: the player to move at the end */
+                     int32_t* out_actions_dev,      /* [n][k][max_plies] or NULL: the moves; entries past plies untouched */
+                     void* stream);
+
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */
 typedef struct azg_forest_cfg {
