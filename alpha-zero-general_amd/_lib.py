@@ -42,6 +42,7 @@ EXPORTS = [
     'azg_selfplay_stats_get', 'azg_selfplay_drain_examples', 'azg_forest_last_kernel_ms', 'azg_forest_enable_timing', 'azg_forest_set_search_params', 'azg_nn_linear', 'azg_nn_linear_ws', 'azg_nn_dw_pool', 'azg_nn_v80_block', 'azg_nn_v80_forward', 'azg_nn_v80_forward_split', 'azg_nn_v80_forward_h2',
     'azg_nn_board_to_x', 'azg_nn_heads_out', 'azg_nn_dw_pool_l', 'azg_nn_board_to_x_ld', 'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
     'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62', 'azg_pick_actions', 'azg_env_playouts',
+    'azg_eval_losses',
 ]
 
 
@@ -112,6 +113,8 @@ def lib():
         L.azg_pick_actions.argtypes = [i, vp, vp, i, i, vp, u64, u64, vp, vp, vp]
     if hasattr(L, 'azg_env_playouts'):                      # (absent from older builds loaded through AZG_LIB for A/B runs)
         L.azg_env_playouts.argtypes = [i, i, vp, vp, vp, i, i, i, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, 'azg_eval_losses'):                       # (absent from older builds loaded through AZG_LIB for A/B runs)
+        L.azg_eval_losses.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, C.c_float, vp, vp, vp, i, vp]
     if hasattr(L, 'azg_debug_rng_u01'):                     # (test aid, include/azg_testaids.h)
         L.azg_debug_rng_u01.argtypes = [u64, u64, u64, i, i, vp, vp]
     L.azg_stream_create_xcd.argtypes = [i, i, C.POINTER(vp)]

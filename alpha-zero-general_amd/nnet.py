@@ -1636,3 +1636,53 @@ class RolloutEvaluator:
         va = torch.as_tensor(np.asarray(valid_actions).astype(np.uint8)).reshape(1, -1).to(self.device)
         pi, v = self.predict_batch(b, va)
         return pi[0].cpu().numpy(), v[0].cpu().numpy()
+
+
+def eval_losses(pi, v, target_pi, z, q, q_weight, active=None, totals=None, accumulate=False):
+    """azg_eval_losses (include/azg.h; csrc/loss.hip.h) on CUDA tensors: the validation losses of B examples from a net's outputs.  pi
+    f32[B, A] PROBABILITIES as predict_batch returns them, v f32[B, P], target_pi f32[B, A], z / q f32[B, P], active u8 / bool[B] or None.
+    -> (rows f64[B, 2]: the row's KL sum and its squared value error, flags int32[B, 2]: top-1 agreement and the number of actions whose
+    probability was below FLT_MIN and was floored there, totals f64[4]: the sums of the four columns over the active rows).  With
+    accumulate=True the sums are added to what `totals` holds (a validation set in chunks: one host read at the end).  rows and flags are
+    allocated here: the C call owns no memory.  One call = two launches on the current stream, nothing synchronised."""
+    B, A = pi.shape
+    P = v.shape[1]
+    for x, shape in ((pi, (B, A)), (target_pi, (B, A)), (v, (B, P)), (z, (B, P)), (q, (B, P))):
+        assert x.dtype == torch.float32 and tuple(x.shape) == shape and x.is_contiguous() and x.device == pi.device, \
+            'eval_losses: dtype / shape / layout of an argument'
+    assert active is None or (active.dtype in (torch.uint8, torch.bool) and active.shape == (B,) and active.is_contiguous()
+                              and active.device == pi.device), 'eval_losses: dtype / shape / layout of active'
+    if totals is None:
+        assert not accumulate, 'eval_losses: accumulate=True needs the totals to add to'
+        totals = torch.zeros(4, dtype=torch.float64, device=pi.device)
+    assert totals.dtype == torch.float64 and totals.shape == (4,) and totals.is_contiguous() and totals.device == pi.device
+    rows = torch.empty((B, 2), dtype=torch.float64, device=pi.device)
+    flags = torch.empty((B, 2), dtype=torch.int32, device=pi.device)
+    from . import _lib
+    _lib.check(_lib.lib().azg_eval_losses(_ptr(pi), _ptr(v), _ptr(target_pi), _ptr(z), _ptr(q), _ptr(active) if active is not None else None,
+                                          B, A, P, C.c_float(float(q_weight)), _ptr(rows), _ptr(flags), _ptr(totals),
+                                          1 if accumulate else 0, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return rows, flags, totals
+
+
+def evaluate_examples(evaluator, cols, q_weight, batch=4096):
+    """The validation losses of GenericNNetWrapper.evaluate (:159-177) for any evaluator with predict_batch (an engine net, a
+    TorchModuleEvaluator, a RolloutEvaluator): cols = (boards int8[n, S], pi f32[n, A], z f32[n, P], valids u8 / bool[n, A], q f32[n, P])
+    tensors or arrays as train.train takes them.  Chunks of `batch` rows go through predict_batch and eval_losses(accumulate=True); one
+    device-to-host read at the end.  -> dict(loss_pi = KL total / n ('batchmean'), loss_v = squared error total / (n P), top1 = the
+    fraction of rows whose policy argmax is the target's, floored = the number of floored probabilities (see eval_losses), n)"""
+    dev = getattr(evaluator, 'device', None) or 'cuda:0'
+    boards, pi, z, valids, q = [torch.as_tensor(x).to(dev) for x in cols[:5]]
+    n = int(boards.shape[0])
+    boards = boards.reshape(n, -1).to(torch.int8).contiguous()
+    valids = valids.reshape(n, -1).to(torch.uint8).contiguous()
+    pi, z, q = (x.reshape(n, -1).to(torch.float32).contiguous() for x in (pi, z, q))
+    P = int(z.shape[1])
+    totals = torch.zeros(4, dtype=torch.float64, device=boards.device)
+    for a in range(0, n, int(batch)):
+        b = min(n, a + int(batch))
+        out_pi, out_v = evaluator.predict_batch(boards[a:b], valids[a:b])
+        eval_losses(out_pi.contiguous(), out_v.contiguous(), pi[a:b], z[a:b], q[a:b], q_weight, totals=totals, accumulate=True)
+    t = totals.cpu().tolist()
+    d = max(n, 1)
+    return dict(loss_pi=t[0] / d, loss_v=t[1] / (d * P), top1=t[2] / d, floored=int(t[3]), n=n)

@@ -5,6 +5,7 @@
                                                        #          nn_version, q_weight  (main.py:124-156, pit.py:44)
     nnet.predict(board, valid_actions) -> (pi f32[A] probabilities, v f32[P])          (GenericNNetWrapper.py:94-120)
     nnet.train(examples[, validation_set, save_folder, every])                          (:44-92)
+    nnet.evaluate(validation_set) -> loss_pi + loss_v; evaluate_details -> the parts    (:159-177)
     nnet.save_checkpoint(folder, filename, additional_keys)                             (:192-205)
     nnet.load_checkpoint(folder, filename) -> the checkpoint dict (state_dict, full_model, embedded args) or None (:207-221)
     nnet.args, nnet.nnet (the trainable torch module), nnet.requestKnowledgeTransfer
@@ -117,6 +118,7 @@ class NNetWrapper:
             dv = _DEFAULT_VERSION.get((game.GAME_ID, game.variant))
             self.nnet = _module_for(game, dv, float(self._arg('dropout', 0.0) or 0.0)) if dv else None
         self._eval, self._eval_batch = None, 0
+        self.validation_history = []                    # (step, validation loss) of the last train() with a validation_set
 
     def _arg(self, k, d=None):
         a = self.args
@@ -143,14 +145,55 @@ class NNetWrapper:
 
     # ---- training (GenericNNetWrapper.train :44-92) ----
     def train(self, examples, validation_set=None, save_folder=None, every=0, seed=None, log=None):
-        cols = decode_examples(examples) if isinstance(examples, (list, tuple)) and len(examples) and not hasattr(examples[0], 'shape') \
-            else examples
+        """With a validation_set: every `every` steps (when (i_batch + steps_per_epoch * epoch) % every == 0, :86) the set is evaluated
+        with the weights and BatchNorm statistics of that moment, the loss goes to `log` (print when None) and into
+        self.validation_history as (step, loss), and where i_batch > 0 and save_folder is given intermediary_<i_batch>.pt is saved (:89-90)"""
+        cols = self._cols(examples)
+        on_step = None
+        self.validation_history = []
+        if validation_set is not None and len(validation_set):
+            every = int(every)
+            if every < 1:
+                raise ValueError('train: a validation_set needs every >= 1 (got %r)' % (every,))
+            vcols = self._cols(validation_set)
+            say = log or print
+
+            def on_step(epoch, i_batch, step):
+                if step % every:
+                    return
+                self._eval = None                                        # the engine kernel must see the current weights
+                loss = self.evaluate(vcols)
+                self.validation_history.append((step, loss))
+                say('step %d: validation loss %.6f' % (step, loss))
+                self.nnet.train()
+                if i_batch > 0 and save_folder:
+                    self.save_checkpoint(save_folder, filename='intermediary_%d.pt' % i_batch)
         lr = self._arg('learn_rate', self._arg('lr', 3e-3))
         hist = _train.train(self.nnet, cols, learn_rate=float(lr), batch_size=int(self._arg('batch_size', 32)),
                             epochs=int(self._arg('epochs', 1)), q_weight=float(self._arg('q_weight', 0.5)),
-                            device=str(self.game.device), seed=seed, log=log, board_shape=self.board_size if self._custom else None)
+                            device=str(self.game.device), seed=seed, log=log, board_shape=self.board_size if self._custom else None,
+                            on_step=on_step)
         self._eval = None
         return hist
+
+    @staticmethod
+    def _cols(examples):
+        """Coach's example list -> the five stacked arrays; five arrays / tensors pass through"""
+        return decode_examples(examples) if isinstance(examples, (list, tuple)) and len(examples) and not hasattr(examples[0], 'shape') \
+            else examples
+
+    # ---- validation (GenericNNetWrapper.evaluate :159-177) ----
+    def evaluate_details(self, validation_set, batch=4096):
+        """dict(loss_pi, loss_v, top1, floored, n) of the net's current weights on validation_set (nnet.evaluate_examples): the forward on
+        the engine's one-launch kernel in chunks of `batch`, the losses by azg_eval_losses, one device-to-host read"""
+        cols = self._cols(validation_set)
+        n = int(cols[0].shape[0])
+        return _nn.evaluate_examples(self.evaluator(max(1, min(n, int(batch)))), cols, float(self._arg('q_weight', 0.5)), batch=batch)
+
+    def evaluate(self, validation_set):
+        """loss_pi + loss_v as a float -- no 0.25 on the value loss here, exactly as the reference (:176)"""
+        d = self.evaluate_details(validation_set)
+        return d['loss_pi'] + d['loss_v']
 
     def loss_pi(self, targets, outputs):
         return _train.loss_pi(targets, outputs)

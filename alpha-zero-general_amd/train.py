@@ -471,10 +471,14 @@ def loss_v(target_z, target_q, out_v, q_weight):                               #
     return torch.sum((t - out_v) ** 2) / (target_z.shape[0] * target_z.shape[-1])
 
 
-def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=0.5, device='cuda:0', seed=None, log=None, board_shape=None):
+def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=0.5, device='cuda:0', seed=None, log=None, board_shape=None,
+          on_step=None):
     """examples = (boards int8[n,S], pi f32[n,A], z f32[n,P], valids u8/bool[n,A], q f32[n,P]) tensors or arrays.
     board_shape: give it for a module that expects the reference's inputs (float boards of getBoardSize(), bool valids:
-    GenericNNetWrapper.py:60-63) instead of the engine modules' flat int8 boards.  Returns the list of (pi loss, v loss) per step."""
+    GenericNNetWrapper.py:60-63) instead of the engine modules' flat int8 boards.
+    on_step(epoch, i_batch, step): called after every optimiser + scheduler step (step = i_batch + steps_per_epoch * epoch) -- the hook of
+    the reference's periodic validation (:86-90); it must leave the module in train() mode.  With None nothing changes, random stream included.
+    Returns the list of (pi loss, v loss) per step."""
     boards, pi, z, valids, q = [torch.as_tensor(np.asarray(x.cpu()) if hasattr(x, 'cpu') else x).to(device) for x in examples[:5]]
     n = boards.shape[0]
     valids = valids.bool()
@@ -491,7 +495,7 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
         gen.manual_seed(seed)
     hist = []
     for ep in range(epochs):
-        for _ in range(steps_per_epoch):
+        for i_batch in range(steps_per_epoch):
             ids = torch.randperm(n, generator=gen)[:batch_size].to(device)   # np.random.choice(n, batch, replace=False) :57
             opt.zero_grad(set_to_none=True)
             out_pi, out_v = module(boards[ids], valids[ids])
@@ -501,6 +505,8 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
             opt.step()
             sched.step()
             hist.append((l_pi.item(), l_v.item()))
+            if on_step is not None:
+                on_step(ep, i_batch, i_batch + steps_per_epoch * ep)
         if log:
             log('epoch %d: pi loss %.4f  v loss %.4f' % (ep + 1, np.mean([h[0] for h in hist[-steps_per_epoch:]]),
                                                          np.mean([h[1] for h in hist[-steps_per_epoch:]])))

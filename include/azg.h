@@ -136,6 +136,29 @@ int azg_env_playouts(int game, int variant,
                      int32_t* out_actions_dev,      /* [n][k][max_plies] or NULL: the moves; entries past plies untouched */
                      void* stream);
 
+/* ---- validation losses on a net's outputs (one wavefront per example row) -------------------------------------------
+   Replaces the loss half of GenericNNetWrapper.evaluate (:159-177; loss_pi / loss_v :179-190) for B examples: pi_dev f32[B][A] are
+   PROBABILITIES as the engine nets return them, v_dev f32[B][P], target_pi_dev f32[B][A], z_dev / q_dev f32[B][P], active_dev u8[B]
+   (NULL = every row).  Per row, in f64:
+     rows_dev[b][0]  = sum over the actions with t > 0 of t (log t - log max(pi, FLT_MIN))   (F.kl_div's xlogy convention: an action
+                       with t == 0 adds exactly 0, whatever pi is);
+     rows_dev[b][1]  = sum_p ((z + q_weight q) / (1 + q_weight) - v)^2                        (q_weight as the f32 it is passed as);
+     flags_dev[b][0] = 1 when the first-index argmax of target_pi is the first-index argmax of pi (np.argmax; a NaN never wins);
+     flags_dev[b][1] = the number of actions with t > 0 and pi < FLT_MIN -- where the floor was applied: an engine probability can
+                       underflow to 0, and the caller sees that here instead of an inf.
+   A row with active == 0 writes zeros and counts for nothing.  Every lane of the row's wave sums its actions l, l + 64, ... in index
+   order and the lanes are combined in one fixed tree: a row's numbers are bit-identical from call to call and do not depend on B.
+   totals_dev f64[4] = the sums of the four columns over the rows, by a second launch of one wave inside this call (rows l, l + 64, ...
+   in order, then the same tree; no atomics); with accumulate != 0 they are ADDED to what totals_dev holds, so a validation set
+   evaluated in chunks needs one host read at the end.  loss_pi = totals[0] / n, loss_v = totals[1] / (n P).
+   rows_dev, flags_dev and totals_dev are REQUIRED: the caller owns them (azg_amd.nnet.eval_losses allocates them), the call owns no
+   memory.  B == 0 launches the totals pass alone (without accumulate it zeroes totals_dev) and needs no other pointer.  B < 0, A < 1,
+   P outside 1 .. 8, B or A above 2^31 - 65, q_weight <= -1 (or NaN) or a NULL required pointer is an error and launches nothing.  No
+   synchronisation and no allocation: the call can sit inside a captured graph. */
+int azg_eval_losses(const float* pi_dev, const float* v_dev, const float* target_pi_dev, const float* z_dev, const float* q_dev,
+                    const uint8_t* active_dev, int B, int A, int P, float q_weight, double* rows_dev, int32_t* flags_dev,
+                    double* totals_dev, int accumulate, void* stream);
+
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */
 typedef struct azg_forest_cfg {
