@@ -134,7 +134,7 @@ def lib():
     L.azg_nn_board_to_x.argtypes = [vp, vp, i, i, vp]
     L.azg_nn_s78_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
     L.azg_nn_s78_forward_split.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
-    L.azg_nn_s78_forward_h2.argtypes = [vp, vp, vp, C.c_float, C.c_float, i, i, i, i, vp, vp, vp]
+    L.azg_nn_s78_forward_h2.argtypes = [vp, vp, vp, C.c_float, C.c_float, i, i, i, i, vp, vp, vp, vp]
     L.azg_nn_aba21_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
     L.azg_nn_bot_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
     L.azg_nn_sw62_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]

@@ -550,7 +550,7 @@ struct NetV80 {                                // Splendor 2 players: k_v80_net_
         h2_net_body<12, true>(lds, &A->W, A->aleaf, (const uint8_t*)A->aleaf, A->F.T, G::P, A->pi, A->v, 0, sidx);
     }
 };
-constexpr int C5_NET_LDS = C5_LDS_LEAD + 2 * 202 * 128 + 65536 + (2 * 25 * 162 + 25 * 64 + 64 * 2 + 64) * 4;      // (azg_nn.hip conv5_launch)
+constexpr int C5_NET_LDS = (int)C5_LDS_H2;
 struct NetC5 {                                 // Santorini no-gods: k_conv5_net<5, 162, 2, 2>'s body, 8 leaves per forward
     using G = SantoriniDev<1>;
     static constexpr int BS = 8, LDS = (C5_NET_LDS + 255) / 256 * 256;
@@ -902,16 +902,7 @@ __global__ __launch_bounds__(768) void k_async_net(const AsyncArgs* args) {
 template <class G>
 static int async_launch_select(const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
     static_assert(azg::ASYNC_SEL_WAVES * azg::RoundLds<G>::STRIDE + sizeof(azg::AsyncSelLds) <= 160 * 1024, "the descent workgroup's LDS fits the CU");
-    static bool attr[64];                       // (per device: a function attribute belongs to the device that was current when it was set)
-    int device = 0;
-    HIPCHK(hipGetDevice(&device));
-    if (device >= 0 && device < 64 && !attr[device]) {
-        HIPCHK(hipFuncSetAttribute((const void*)azg::k_async_select<G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr[device] = true;
-    }
-    azg::k_async_select<G><<<dim3(n_sel), dim3(azg::ASYNC_SEL_WAVES * 64), azg::ASYNC_SEL_WAVES * azg::RoundLds<G>::STRIDE + (int)sizeof(azg::AsyncSelLds), s>>>(devbuf);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<azg::k_async_select<G>>(dim3(n_sel), dim3(azg::ASYNC_SEL_WAVES * 64), azg::ASYNC_SEL_WAVES * azg::RoundLds<G>::STRIDE + sizeof(azg::AsyncSelLds), s, devbuf);
 }
 int azg_async_launch_select(int net_kind, const azg::AsyncArgs* devbuf, int n_sel, hipStream_t s) {
     using Launch = int (*)(const azg::AsyncArgs*, int, hipStream_t);
@@ -1033,34 +1024,26 @@ __global__ __launch_bounds__(256) void k_async_requeue(const AsyncArgs* args) {
 
 template <class NET>
 static int async_launch_net(const AsyncArgs* devbuf, int n_net, hipStream_t s) {
-    k_async_net<NET><<<dim3(n_net), dim3(768), NET::LDS + ASYNC_DESC_BYTES, s>>>(devbuf);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-template <class NET>
-static int async_net_attr() {
-    HIPCHK(hipFuncSetAttribute((const void*)k_async_net<NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    return 0;
+    return launch_lds<k_async_net<NET>>(dim3(n_net), dim3(768), NET::LDS + ASYNC_DESC_BYTES, s, devbuf);
 }
 // The table of kinds, generated from AZG_ASYNC_KINDS (above): per row the forest it serves, its texts, the leaf record's stride and the samples
 // of a forward (both read off the row's types), the weight table the net reads, the default split of the CUs, the MobileNet-1d geometry it
-// answers to, and its launchers -- the engine net's, the hash-net's, and the net kernel's LDS attribute.
+// answers to, and its launchers -- the engine net's and the hash-net's.
 enum AsyncWt { WT_V80, WT_C5, WT_MB, WT_SW };
 constexpr int ASYNC_NO_GEOMETRY = -1;
 using AsyncNetLaunch = int (*)(const AsyncArgs*, int, hipStream_t);
 struct AsyncKind {
     int game, variant; const char* name; const char* only; int leaf_stride, bs, wt, net_256; bool cap_trees; int geometry; const char* geometry_name;
-    AsyncNetLaunch launch_net, launch_hashnet; int (*net_attr)();
+    AsyncNetLaunch launch_net, launch_hashnet;
 };
 static_assert(AsyncLeaf<SplendorDev<2>>::STRIDE == H2_AL_STRIDE && AsyncLeaf<SplendorDev<2>>::MASK_OFF == H2_AL_MASK, "leaf record layout shared with the net kernel");
 static_assert(AsyncLeaf<SantoriniDev<1>>::STRIDE == C5_AL_STRIDE && AsyncLeaf<SantoriniDev<1>>::MASK_OFF == C5_AL_MASK, "leaf record layout shared with the net kernel");
 #ifdef AZG_ASYNC_SANTORINI11
 struct NetNone { static constexpr int BS = 16; };          // a descent kernel without an engine net: the hash-net only
 template <> int async_launch_net<NetNone>(const AsyncArgs*, int, hipStream_t) { return fail("no engine net for this game in the pipeline"); }
-template <> int async_net_attr<NetNone>() { return 0; }
 #endif
 #define X(G, NET, GAME, VARIANT, NAME, ONLY, WT, NET_256, CAP_TREES, GEOMETRY)                                                                  \
-    {GAME, VARIANT, NAME, ONLY, AsyncLeaf<G>::STRIDE, NET::BS, WT, NET_256, CAP_TREES, GEOMETRY, #GEOMETRY, &async_launch_net<NET>, &async_launch_net<NetHash<G>>, &async_net_attr<NET>},
+    {GAME, VARIANT, NAME, ONLY, AsyncLeaf<G>::STRIDE, NET::BS, WT, NET_256, CAP_TREES, GEOMETRY, #GEOMETRY, &async_launch_net<NET>, &async_launch_net<NetHash<G>>},
 static const AsyncKind ASYNC_KINDS[] = {AZG_ASYNC_KINDS(X)};
 #undef X
 constexpr int ASYNC_NKINDS = (int)(sizeof(ASYNC_KINDS) / sizeof(ASYNC_KINDS[0]));
@@ -1132,8 +1115,6 @@ static int async_rounds_impl(const char* who, int kind, int hash, azg_forest* f,
         HIPCHK(hipStreamCreateWithPriority(&b, hipStreamNonBlocking, hi));
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, device));
-        for (int k = 0; k < ASYNC_NKINDS; k++)
-            if (ASYNC_KINDS[k].net_attr()) return -1;
         D.net_stream = a; D.sel_stream = b; D.n_cu = prop.multiProcessorCount;
     }
     const int n_cu = D.n_cu;

@@ -156,11 +156,6 @@ extern "C" int azg_forest_rounds_v80_h2(azg_forest* f, int8_t* leaf_states, uint
     if (game != AZG_SPLENDOR || variant != 2) return fail("azg_forest_rounds_v80_h2: Splendor 2 players only (the V80 geometry of nn_v80_h2.hip.h)");
     const int noise = (alpha != 0.0 && noise_stride == -2) ? 1 : 0;
     using G = SplendorDev<2>;
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_rounds_v80<G>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
     // the argument block lives in device memory, one per (forest, buffers, weights) combination; it is (re)written -- ordered on the
     // launch stream, from a host copy that stays alive -- whenever the combination changes (also under stream capture: the copy becomes a
     // graph node in front of the kernel node)
@@ -184,8 +179,6 @@ extern "C" int azg_forest_rounds_v80_h2(azg_forest* f, int8_t* leaf_states, uint
         sl->host = want;
         HIPCHK(hipMemcpyAsync(sl->devbuf, &sl->host, sizeof(RoundArgs), hipMemcpyHostToDevice, (hipStream_t)stream));
     }
-    k_rounds_v80<G><<<dim3((dev->T + 15) / 16), dim3(1024), H2_LDS, (hipStream_t)stream>>>(sl->devbuf, rounds);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_rounds_v80<G>>(dim3((dev->T + 15) / 16), dim3(1024), H2_LDS, (hipStream_t)stream, sl->devbuf, rounds);
 }
 #endif  // AZG_FUSED_DEVICE_ONLY

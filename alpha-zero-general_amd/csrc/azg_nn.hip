@@ -41,16 +41,8 @@ static int launch_linear(const float* A, int lda, const float* Wp, const float* 
         grid = (tiles + 3) / 4;
         if (grid > 512) grid = 512;
     }
-    if (lds > 160 * 1024) return fail("azg_nn_linear: weight tile exceeds LDS");
-    static bool attr_done = false;
-    if (lds > 64 * 1024 && !attr_done) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_linear<NT, KSPLIT, NCH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done = true;
-    }
-    k_linear<NT, KSPLIT, NCH><<<dim3(grid), dim3(256), lds, s>>>(A, lda, Wp, bias, R, ldr, rowscale, rpg, out, ldc, M, K, Kp,
-                                                                  N, act);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (lds > AZG_LDS_MAX) return fail("azg_nn_linear: weight tile exceeds LDS");
+    return launch_lds<k_linear<NT, KSPLIT, NCH>>(dim3(grid), dim3(256), lds, s, A, lda, Wp, bias, R, ldr, rowscale, rpg, out, ldc, M, K, Kp, N, act);
 }
 
 extern "C" int azg_nn_linear(const float* A, int lda, const float* Wp, int Kp, int NP, const float* bias, const float* R,
@@ -147,20 +139,10 @@ extern "C" int azg_nn_dw_pool(float* H, int ldh, const float* Wd, const float* s
     return azg_nn_dw_pool_l(H, ldh, Wd, sd, bd, pooled, B, E, 7, act, pool_max, stream);
 }
 
-static constexpr size_t V80_LDS = (size_t)(112 * 60 + 112 * 172 + 2 * 16 * 172 + 16 * 52 + 64) * sizeof(float);
-
 template <int A_, int P_, int M_>
 static int launch_v80(const float* xin, float* xout, const V80BlockW& W, int B, const int8_t* boards, const V80NetW& N,
                       const uint8_t* valid, float* pi, float* v, int P, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_v80_block<A_, P_, M_>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-        attr = true;
-    }
-    k_v80_block<A_, P_, M_><<<dim3((B + 15) / 16), dim3(768), V80_LDS, s>>>(xin, xout, W, B, boards, N, valid, pi, v, P);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_v80_block<A_, P_, M_>>(dim3((B + 15) / 16), dim3(768), V80_LDS, s, xin, xout, W, B, boards, N, valid, pi, v, P);
 }
 
 extern "C" int azg_nn_v80_block(const float* xin, float* xout, const float* const* w /* 11 device pointers */, int B,
@@ -188,32 +170,14 @@ static int v80_forward(const int8_t* boards, const uint8_t* valid, const float* 
     V80NetW Nv{nullptr, nullptr, w[39], w[40], w[41], w[42]};
     hipStream_t s = (hipStream_t)stream;
     // V80 geometry (SplendorNNet.py:262-283): trunk ReLU + mean-SE, both heads Hardswish + max-SE
-    if (split) {
-        static bool attr_s = false;
-        constexpr size_t lds_s = (size_t)3 * 112 * 128 + (V80_LDS - (size_t)112 * 60 * sizeof(float)) + 12288;
-        if (!attr_s) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_v80_net_spx, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_s = true;
-        }
-        k_v80_net_spx<<<dim3((B + 15) / 16), dim3(768), lds_s, s>>>(Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
+    if (split) return launch_lds<k_v80_net_spx>(dim3((B + 15) / 16), dim3(768), V80_SPX_LDS, s, Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
     if (getenv("AZG_NN_THREE_LAUNCHES")) {       // the per-block path (kept for A/B measurements)
         if (launch_v80<1, 0, 1>(nullptr, x_trunk, Wt, B, boards, N0, nullptr, nullptr, nullptr, P, s)) return -1;
         if (launch_v80<2, 1, 2>(x_trunk, nullptr, Wp, B, nullptr, Np, valid, pi, nullptr, P, s)) return -1;
         if (launch_v80<2, 1, 3>(x_trunk, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v, P, s)) return -1;
         return 0;
     }
-    static bool attr = false;
-    constexpr size_t lds = V80_LDS + (size_t)112 * 60 * sizeof(float);
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_v80_net, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    k_v80_net<<<dim3((B + 15) / 16), dim3(768), lds, s>>>(Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_v80_net>(dim3((B + 15) / 16), dim3(768), V80_NET_LDS, s, Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
 }
 
 
@@ -234,16 +198,10 @@ extern "C" int azg_nn_v80_forward_h2(const int8_t* boards, const uint8_t* valid,
     if (P < 2 || P > 4) return fail("azg_nn_v80_forward_h2: 2 <= P <= 4");
     const H2Weights HW = h2_weights(w, descale);
     hipStream_t s = (hipStream_t)stream;
-    static int waves_h2 = 0;          // AZG_V80_WAVES=16: the 16-wave / 128-VGPR variant (the form the fused round kernel uses); default 12
-    if (!waves_h2) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_v80_net_h2<12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(hipFuncSetAttribute((const void*)k_v80_net_h2<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        waves_h2 = (getenv("AZG_V80_WAVES") && atoi(getenv("AZG_V80_WAVES")) == 16) ? 16 : 12;
-    }
-    if (waves_h2 == 16) k_v80_net_h2<16><<<dim3((B + 15) / 16), dim3(1024), H2_LDS, s>>>(HW, boards, valid, B, P, pi, v);
-    else k_v80_net_h2<12><<<dim3((B + 15) / 16), dim3(768), H2_LDS, s>>>(HW, boards, valid, B, P, pi, v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    // AZG_V80_WAVES=16: the 16-wave / 128-VGPR variant (the form the fused round kernel uses); default 12
+    static const int waves_h2 = (getenv("AZG_V80_WAVES") && atoi(getenv("AZG_V80_WAVES")) == 16) ? 16 : 12;
+    if (waves_h2 == 16) return launch_lds<k_v80_net_h2<16>>(dim3((B + 15) / 16), dim3(1024), H2_LDS, s, HW, boards, valid, B, P, pi, v);
+    return launch_lds<k_v80_net_h2<12>>(dim3((B + 15) / 16), dim3(768), H2_LDS, s, HW, boards, valid, B, P, pi, v);
 }
 
 #ifdef AZG_NN_PHASE_TIMES
@@ -272,14 +230,7 @@ template <class CF, bool H2>
 static int launch_mb1d(const Mb1dNetW& N, const int8_t* boards, const uint8_t* valid, int B, float* pi, float* v, hipStream_t s) {
     constexpr size_t lds = (size_t)CF::LDS_FLOATS * sizeof(float);
     static_assert(lds <= 160 * 1024, "geometry does not fit the LDS of a CU");
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_mb1d_net<CF, H2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    k_mb1d_net<CF, H2><<<dim3((B + CF::NS - 1) / CF::NS), dim3(768), lds, s>>>(N, boards, valid, B, pi, v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_mb1d_net<CF, H2>>(dim3((B + CF::NS - 1) / CF::NS), dim3(768), lds, s, N, boards, valid, B, pi, v);
 }
 
 template <bool H2>
@@ -328,35 +279,11 @@ static int conv5_launch(const int8_t* boards, const uint8_t* valid, const float*
     if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_conv5_forward: null/empty argument");
     if (n_blocks != 5 || A != 162 || P != 2) return fail("azg_nn_conv5_forward: built for 5 residual blocks, A = 162, P = 2");
     Conv5NetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13]};
-    static bool attr[3] = {false, false, false};
-    if (split == 2) {
-        // two activation tiles of two f16 planes (+ two zero rows each); the second tile also holds the f32 board staging tile at the
-        // start and the f32 trunk output + head buffers at the end of the kernel (54.4 KB + 9.8 KB)
-        // + the LDS copies of the head / FC matrices (k_conv5_net: WST_N floats)
-        constexpr size_t lds = (size_t)C5_LDS_LEAD + (size_t)2 * 202 * 128 + 65536 + (size_t)(2 * 25 * 162 + 25 * 64 + 64 * 2 + 64) * sizeof(float);
-        static_assert(lds <= 160 * 1024, "k_conv5_net<.., 2>: LDS");
-        if (!attr[2]) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_conv5_net<5, 162, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr[2] = true;
-        }
-        k_conv5_net<5, 162, 2, 2><<<dim3((B + 7) / 8), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v, descale);
-    } else if (split) {
-        constexpr size_t lds = (size_t)2 * 3 * 202 * 128;              // two activation tiles of three bf16 planes (+ two zero rows each)
-        if (!attr[1]) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_conv5_net<5, 162, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr[1] = true;
-        }
-        k_conv5_net<5, 162, 2, 3><<<dim3((B + 7) / 8), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v, 1.f);
-    } else {
-        constexpr size_t lds = (size_t)2 * 200 * 68 * sizeof(float);
-        if (!attr[0]) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_conv5_net<5, 162, 2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr[0] = true;
-        }
-        k_conv5_net<5, 162, 2, 0><<<dim3((B + 7) / 8), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v, 1.f);
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
+    const dim3 grid((B + 7) / 8), block(768);
+    hipStream_t s = (hipStream_t)stream;
+    if (split == 2) return launch_lds<k_conv5_net<5, 162, 2, 2>>(grid, block, C5_LDS_H2, s, N, boards, valid, B, pi, v, descale);
+    if (split) return launch_lds<k_conv5_net<5, 162, 2, 3>>(grid, block, C5_LDS_BF16X3, s, N, boards, valid, B, pi, v, 1.f);
+    return launch_lds<k_conv5_net<5, 162, 2, 0>>(grid, block, C5_LDS_F32, s, N, boards, valid, B, pi, v, 1.f);
 }
 
 extern "C" int azg_nn_conv5_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_blocks, int A,
@@ -376,82 +303,27 @@ extern "C" int azg_nn_conv5_forward_h2(const int8_t* boards, const uint8_t* vali
 
 // ---- Santorini-with-gods net V78 (10 InvertedResidual blocks, A = 1782, P = 2): trunk + value head, then the policy FC (nn_conv5x5.hip.h) ----
 static int s78_launch(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_blocks, int A, int P, int B, float* pi,
-                      float* v, void* stream, int split /* 0 f32, 3 bf16 x 3, 2 f16 x 2 */, float ds_e = 1.f, float ds_p = 1.f) {
+                      float* v, void* stream, int split /* 0 f32, 3 bf16 x 3, 2 f16 x 2 */, float ds_e = 1.f, float ds_p = 1.f,
+                      float* logits_ws = nullptr /* f16 x 2: non-null = the two-launch policy FC */) {
     if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_s78_forward: null/empty argument");
     if (n_blocks != 10 || A != 1782 || P != 2) return fail("azg_nn_s78_forward: built for 10 blocks, A = 1782, P = 2");
     S78NetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], w[15], w[16], w[17], w[18]};
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 block(768), grid16((B + 15) / 16);
     if (split == 2) {
-        constexpr size_t lds = (size_t)(2 + 4) * 202 * 128 + 8 * 32 * sizeof(float);      // X: two f16 planes; H: the f32 expanded tile + two f16 planes behind it
-        static bool attr = false;
-        if (!attr) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_s78_net_split<10, 1782, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr = true;
-        }
-        k_s78_net_split<10, 1782, 2, 2><<<dim3((B + 7) / 8), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v, ds_e, ds_p);
+        if (launch_lds<k_s78_net_split<10, 1782, 2, 2>>(dim3((B + 7) / 8), block, S78_LDS_H2, s, N, boards, valid, B, pi, v, ds_e, ds_p)) return -1;
     } else if (split) {
-        constexpr size_t lds = (size_t)2 * 3 * 202 * 128 + 8 * 32 * sizeof(float);
-        static bool attr = false;
-        if (!attr) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_s78_net_split<10, 1782, 2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr = true;
-        }
-        k_s78_net_split<10, 1782, 2, 3><<<dim3((B + 7) / 8), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v, 1.f, 1.f);
+        if (launch_lds<k_s78_net_split<10, 1782, 2, 3>>(dim3((B + 7) / 8), block, S78_LDS_BF16X3, s, N, boards, valid, B, pi, v, 1.f, 1.f)) return -1;
     } else {
-        constexpr size_t lds = (size_t)(112 * 68 + 112 * 196 + 4 * 32) * sizeof(float);
-        static bool attr = false;
-        if (!attr) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_s78_net<10, 1782, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr = true;
-        }
-        k_s78_net<10, 1782, 2><<<dim3((B + 3) / 4), dim3(768), lds, (hipStream_t)stream>>>(N, boards, valid, B, pi, v);
+        if (launch_lds<k_s78_net<10, 1782, 2>>(dim3((B + 3) / 4), block, S78_LDS_F32, s, N, boards, valid, B, pi, v)) return -1;
     }
-    HIPCHK(hipGetLastError());
-    static const int pol2 = getenv("AZG_S78_POLICY2") ? atoi(getenv("AZG_S78_POLICY2")) : 1;    // (0: the one-launch form, k_s78_policy_h2)
-    if (split == 2 && pol2) {               // policy FC in two launches: 64 samples x a quarter of the columns per workgroup, then the softmax
-        // workspace for the raw logits [B][1792] (the pi rows hold the policy features until every column quarter has read them): kept per
-        // device, grown on demand (the first call of a size happens in the warm-up rounds, before any graph capture)
-        static float* ws[64];
-        static size_t ws_rows[64];
-        int dv = 0;
-        HIPCHK(hipGetDevice(&dv));
-        if (dv < 0 || dv >= 64) return fail("azg_nn_s78_forward_h2: device index");
-        if (ws_rows[dv] < (size_t)B) {
-            if (ws[dv]) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(ws[dv]); ws[dv] = nullptr; ws_rows[dv] = 0; }
-            HIPCHK(hipMalloc(&ws[dv], (size_t)B * 1792 * sizeof(float)));
-            ws_rows[dv] = (size_t)B;
-        }
-        constexpr size_t lds_g = (size_t)2 * 64 * (160 * 2 + 16);
-        static bool attr_g = false;
-        if (!attr_g) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_s78_policy_gemm_h2<1782, 132>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
-            attr_g = true;
-        }
-        k_s78_policy_gemm_h2<1782, 132><<<dim3((B + 63) / 64, 4), dim3(768), lds_g, (hipStream_t)stream>>>((const uint4*)N.Wfp, N.bfp, B, pi, ws[dv]);
-        HIPCHK(hipGetLastError());
-        k_s78_policy_softmax<1782><<<dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(ws[dv], valid, B, pi);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (split == 2) {                       // (the policy FC on f16 x 2 operands as well: w[11] then holds its hi / lo fragments + the descale)
-        constexpr size_t lds_h2 = (size_t)(16 * (160 + 4) + 16 * (112 * 16 + 4)) * sizeof(float);
-        static bool attr_h2 = false;
-        if (!attr_h2) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_s78_policy_h2<1782, 132>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_h2));
-            attr_h2 = true;
-        }
-        k_s78_policy_h2<1782, 132><<<dim3((B + 15) / 16), dim3(768), lds_h2, (hipStream_t)stream>>>((const uint4*)N.Wfp, N.bfp, valid, B, pi);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    constexpr size_t lds_pi = (size_t)(16 * (144 + 4) + 16 * (112 * 16 + 4)) * sizeof(float);
-    static bool attr_pi = false;
-    if (!attr_pi) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_s78_policy<1782, 132>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pi));
-        attr_pi = true;
-    }
-    k_s78_policy<1782, 132><<<dim3((B + 15) / 16), dim3(768), lds_pi, (hipStream_t)stream>>>(N.Wfp, N.bfp, valid, B, pi);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (split != 2) return launch_lds<k_s78_policy<1782, 132>>(grid16, block, S78_POLICY_LDS, s, N.Wfp, N.bfp, valid, B, pi);
+    // the policy FC on f16 x 2 operands as well (w[11] then holds its hi / lo fragments + the descale): in one launch, or -- with the caller's
+    // workspace for the raw logits [B][1792] (the pi rows hold the policy features until every column quarter has read them) -- in two: 64
+    // samples x a quarter of the columns per workgroup, then the softmax
+    if (!logits_ws) return launch_lds<k_s78_policy_h2<1782, 132>>(grid16, block, S78_POLICY_H2_LDS, s, (const uint4*)N.Wfp, N.bfp, valid, B, pi);
+    if (launch_lds<k_s78_policy_gemm_h2<1782, 132>>(dim3((B + 63) / 64, 4), block, S78_POLICY_GEMM_LDS, s, (const uint4*)N.Wfp, N.bfp, B, pi, logits_ws)) return -1;
+    return launch_lds<k_s78_policy_softmax<1782>>(dim3((B + 3) / 4), dim3(256), 0, s, logits_ws, valid, B, pi);
 }
 
 extern "C" int azg_nn_s78_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_blocks, int A, int P,
@@ -465,8 +337,8 @@ extern "C" int azg_nn_s78_forward_split(const int8_t* boards, const uint8_t* val
 }
 
 extern "C" int azg_nn_s78_forward_h2(const int8_t* boards, const uint8_t* valid, const float* const* w, float ds_e, float ds_p, int n_blocks,
-                                     int A, int P, int B, float* pi, float* v, void* stream) {
-    return s78_launch(boards, valid, w, n_blocks, A, P, B, pi, v, stream, 2, ds_e, ds_p);
+                                     int A, int P, int B, float* pi, float* v, float* logits_ws, void* stream) {
+    return s78_launch(boards, valid, w, n_blocks, A, P, B, pi, v, stream, 2, ds_e, ds_p, logits_ws);
 }
 
 // ---- Abalone net V21 (4 InvertedResidual blocks on the 9 x 9 grid, A = 3402, P = 2): one launch, 4 samples per workgroup (nn_abalone.hip.h) ----
@@ -477,14 +349,7 @@ extern "C" int azg_nn_aba21_forward(const int8_t* boards, const uint8_t* valid, 
     for (int i = 0; i < 16; i++)
         if (!w[i]) return fail("azg_nn_aba21_forward: null weight pointer");
     Aba21NetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12], w[13], w[14], w[15]};
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_aba21_net<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ABA_LDS));
-        attr = true;
-    }
-    k_aba21_net<4, 2><<<dim3((B + ABA_NS - 1) / ABA_NS), dim3(ABA_THREADS), ABA_LDS, (hipStream_t)stream>>>(N, boards, valid, B, pi, v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_aba21_net<4, 2>>(dim3((B + ABA_NS - 1) / ABA_NS), dim3(ABA_THREADS), ABA_LDS, (hipStream_t)stream, N, boards, valid, B, pi, v);
 }
 
 // ---- Smallworld net V62 (3-layer transformer encoder over the N tokens, P = 2 / 3 / 4): one launch, 4 / 3 / 2 samples per workgroup
@@ -526,14 +391,7 @@ extern "C" int azg_nn_akr31_forward(const int8_t* boards, const uint8_t* valid, 
 // ---- Botanik nets V10 / V11 (1-d branch + 1 or 2 machine branches, A = 428, P = 2): one launch, 8 samples per workgroup (nn_botanik.hip.h) ----
 template <int NM>
 static int bot_launch(const BotNetW& N, const int8_t* boards, const uint8_t* valid, int B, float* pi, float* v, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_bot_net<NM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BOT_LDS));
-        attr = true;
-    }
-    k_bot_net<NM><<<dim3((B + BOT_NS - 1) / BOT_NS), dim3(BOT_THREADS), BOT_LDS, s>>>(N, boards, valid, B, pi, v);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return launch_lds<k_bot_net<NM>>(dim3((B + BOT_NS - 1) / BOT_NS), dim3(BOT_THREADS), BOT_LDS, s, N, boards, valid, B, pi, v);
 }
 
 extern "C" int azg_nn_bot_forward(const int8_t* boards, const uint8_t* valid, const float* const* w, int n_mach, int P, int A, int B,

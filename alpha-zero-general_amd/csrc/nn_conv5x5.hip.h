@@ -961,6 +961,14 @@ __device__ __forceinline__ void conv5_net_body(float* smem, const Conv5NetWC Np,
 #undef N
 
 // SPLIT: the trunk on bf16 x 3 operands (above; N.Wc then points to the split fragments); LDS = 2 tiles x 3 planes x (ROWS + 1) x 128 B
+// dynamic LDS of k_conv5_net<5, 162, 2, SPLIT> (bytes):
+constexpr size_t C5_LDS_F32 = (size_t)2 * 200 * 68 * sizeof(float);       // SPLIT 0: two f32 activation tiles [200][68]
+constexpr size_t C5_LDS_BF16X3 = (size_t)2 * 3 * 202 * 128;              // SPLIT 3: two activation tiles of three bf16 planes (+ two zero rows each)
+// SPLIT 2: two activation tiles of two f16 planes (+ two zero rows each); the second tile also holds the f32 board staging tile at the
+// start and the f32 trunk output + head buffers at the end of the kernel (54.4 KB + 9.8 KB)
+// + the LDS copies of the head / FC matrices (conv5_net_body: WST_N floats)
+constexpr size_t C5_LDS_H2 = (size_t)C5_LDS_LEAD + (size_t)2 * 202 * 128 + 65536 + (size_t)(2 * 25 * 162 + 25 * 64 + 64 * 2 + 64) * sizeof(float);
+static_assert(C5_LDS_F32 <= 160 * 1024 && C5_LDS_BF16X3 <= 160 * 1024 && C5_LDS_H2 <= 160 * 1024, "k_conv5_net: LDS");
 template <int NB, int A, int P, int SPLIT = 0>
 __global__ __launch_bounds__(768) void k_conv5_net(Conv5NetW N /* first argument: offset 0 of the kernel argument segment, read through it */,
                                                    const int8_t* __restrict__ boards,
@@ -1148,6 +1156,7 @@ __device__ __forceinline__ void s78_heads_lds(const S78HeadPf& pf, const float* 
     }
 }
 
+constexpr size_t S78_LDS_F32 = (size_t)(112 * 68 + 112 * 196 + 4 * 32) * sizeof(float);      // k_s78_net<10, 1782, 2>: X [112][68], H [112][196], META [4][32]
 template <int NB, int A, int P>
 __global__ __launch_bounds__(768) void k_s78_net(S78NetW N, const int8_t* __restrict__ boards, const uint8_t* __restrict__ valid,
                                                  int B, float* __restrict__ pi_out, float* __restrict__ v_out) {
@@ -1250,6 +1259,10 @@ __global__ __launch_bounds__(768) void k_s78_net(S78NetW N, const int8_t* __rest
 #ifndef AZG_S78_W2
 #define AZG_S78_W2 1                        /* 0: one column tile per wave (4 x 3), the form of rounds 2-5 */
 #endif
+// dynamic LDS of k_s78_net_split<10, 1782, 2, NPL> (bytes), 8 samples = 200 cells (+ two zero rows per plane), META [8][32] behind the tiles:
+constexpr size_t S78_LDS_BF16X3 = (size_t)2 * 3 * 202 * 128 + 8 * 32 * sizeof(float);         // NPL 3: X and the third of H, three bf16 planes each
+constexpr size_t S78_LDS_H2 = (size_t)(2 + 4) * 202 * 128 + 8 * 32 * sizeof(float);           // NPL 2: X: two f16 planes; H: the f32 expanded tile + two f16 planes behind it
+static_assert(S78_LDS_F32 <= 160 * 1024 && S78_LDS_BF16X3 <= 160 * 1024 && S78_LDS_H2 <= 160 * 1024, "k_s78_net*: LDS");
 template <int NB, int A, int P, int NPL = 3, int NS = 8>
 __global__ __launch_bounds__(768) void k_s78_net_split(S78NetW N, const int8_t* __restrict__ boards, const uint8_t* __restrict__ valid,
                                                        int B, float* __restrict__ pi_out, float* __restrict__ v_out, float ds_e, float ds_p) {
@@ -1549,6 +1562,7 @@ __global__ __launch_bounds__(768) void k_s78_net_split(S78NetW N, const int8_t* 
 // (HeadWithMeta :62-69), pi = exp(log_softmax(where(valid, logits, -1e8))).  feat = the first FP floats of each pi row (written by
 // k_s78_net), K padded to 144.  The activation fragments of the 16 samples stay in registers, the 12 waves stream the weight
 // fragments of their column tiles (1 KB per K chunk), logits live in LDS [16][LS].
+constexpr size_t S78_POLICY_LDS = (size_t)(16 * (144 + 4) + 16 * (112 * 16 + 4)) * sizeof(float);       // k_s78_policy<1782, 132>: FEAT [16][FS], LG [16][LS]
 template <int A, int FP>
 __global__ __launch_bounds__(768) void k_s78_policy(const float* __restrict__ Wfrag, const float* __restrict__ bias,
                                                     const uint8_t* __restrict__ valid, int B, float* __restrict__ pi) {
@@ -1624,6 +1638,7 @@ __global__ __launch_bounds__(768) void k_s78_policy(const float* __restrict__ Wf
 // (K 132 -> 160, N 1782 -> 1792, zero padded; element = W_plane[32*chunk + 8*(lane>>4) + j][16*ct + (lane&15)]) followed by ONE float:
 // the descale 2^-k / 64 (the feature operand holds 64 * x like every activation plane).  The 16 samples' feature fragments stay in
 // registers, a wave streams the fragments of its column tiles two tiles ahead of the MFMAs.
+constexpr size_t S78_POLICY_H2_LDS = (size_t)(16 * (160 + 4) + 16 * (112 * 16 + 4)) * sizeof(float);    // k_s78_policy_h2<1782, 132>: FEAT [16][FS], LG [16][LS]
 template <int A, int FP>
 __global__ __launch_bounds__(768) void k_s78_policy_h2(const uint4* __restrict__ Wfrag, const float* __restrict__ bias,
                                                        const uint8_t* __restrict__ valid, int B, float* __restrict__ pi) {
@@ -1703,6 +1718,8 @@ __global__ __launch_bounds__(768) void k_s78_policy_h2(const uint4* __restrict__
 // features of its 64 samples sit in LDS as f16 hi / lo planes (row stride 336 B: conflict-free 16-byte operand reads), raw logits go to a
 // workspace [B][1792] (the pi rows still hold the FEATURES the other three quarters of the same samples read), and k_s78_policy_softmax
 // normalises them into pi, one wave per sample.
+constexpr size_t S78_POLICY_GEMM_LDS = (size_t)2 * 64 * (160 * 2 + 16);                                   // k_s78_policy_gemm_h2<1782, 132>: FH, FL [64][RS]
+static_assert(S78_POLICY_LDS <= 160 * 1024 && S78_POLICY_H2_LDS <= 160 * 1024 && S78_POLICY_GEMM_LDS <= 160 * 1024, "k_s78_policy*: LDS");
 template <int A, int FP>
 __global__ __launch_bounds__(768) void k_s78_policy_gemm_h2(const uint4* __restrict__ Wfrag, const float* __restrict__ bias, int B,
                                                             const float* __restrict__ pi_feat, float* __restrict__ logits) {

@@ -833,6 +833,12 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
     }
 }
 
+// dynamic LDS of the three kernels below (bytes): k_v80_block = X [112][60] + H of v80_block_body; k_v80_net = + a second [112][60] tile;
+// k_v80_net_spx = three bf16 planes [112][64] instead of X, + 12 KB behind H (the head blocks' output tile)
+constexpr size_t V80_LDS = (size_t)(112 * 60 + 112 * 172 + 2 * 16 * 172 + 16 * 52 + 64) * sizeof(float);
+constexpr size_t V80_NET_LDS = V80_LDS + (size_t)112 * 60 * sizeof(float);
+constexpr size_t V80_SPX_LDS = (size_t)3 * 112 * 128 + (V80_LDS - (size_t)112 * 60 * sizeof(float)) + 12288;
+static_assert(V80_LDS <= 160 * 1024 && V80_NET_LDS <= 160 * 1024 && V80_SPX_LDS <= 160 * 1024, "k_v80_*: LDS");
 template <int ACT, int POOLMAX, int MODE>
 AZG_NN_KERNEL __global__ __launch_bounds__(768) void k_v80_block(const float* __restrict__ xin, float* __restrict__ xout, V80BlockW W,
                                                    int B, const int8_t* __restrict__ boards, V80NetW N,

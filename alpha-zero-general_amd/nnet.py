@@ -9,6 +9,7 @@ plain GEMM, with BatchNorm folded into the GEMM weights (eval mode) and the Flat
 head Linear.  It loads the reference's state_dict key names unchanged (checkpoint compatibility)."""
 import copy
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -24,6 +25,45 @@ def _fold_bn(sd, prefix, eps=1e-5):
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def _pow2_scale(maxabs):
+    """the exponent k of the f16 x 2 operands: maxabs * 2^k in (2^11, 2^12] (an all-zero matrix: any scale).  The kernels multiply
+    their accumulators by _descale(k)"""
+    return 12 - int(math.ceil(math.log2(max(float(maxabs), 1e-30))))
+
+
+def _descale(k):
+    return (2.0 ** -k) / 64.0
+
+
+def _split_frag(m, kind, k=0):
+    """zero-padded [K][N] f32 (K % 32 == 0, N % 16 == 0) -> split-precision MFMA fragments [N/16 tiles][K/32 chunks][planes][64 lanes][8]:
+    frag[ct][c][p][lane][j] = plane_p[32c + 8*(lane>>4) + j][16ct + (lane&15)].  kind 'h2': the f16 hi / lo planes of m * 2^k;
+    'bf16x3': the bf16 hi / mid / lo planes of m"""
+    K, N = m.shape
+    assert K % 32 == 0 and N % 16 == 0
+    m = m.contiguous().float()
+    if kind == 'h2':
+        m = m * (2.0 ** k)
+        hi = m.to(torch.float16)
+        planes = [hi, (m - hi.float()).to(torch.float16)]
+    else:
+        assert kind == 'bf16x3'
+        hi = m.to(torch.bfloat16)
+        r1 = m - hi.float()
+        mid = r1.to(torch.bfloat16)
+        planes = [hi, mid, (r1 - mid.float()).to(torch.bfloat16)]
+    assert bool(torch.isfinite(hi.float()).all())
+    pl = torch.stack(planes).view(len(planes), K // 32, 4, 8, N // 16, 16)                # plane, chunk, g, j, tile, r
+    return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                             # tile, chunk, plane, g, r, j
+
+
+def _pad(t, shape):
+    """t zero-padded to `shape` (f32, a fresh tensor)"""
+    out = torch.zeros(shape, dtype=torch.float32, device=t.device)
+    out[tuple(slice(0, n) for n in t.shape)] = t
+    return out
 
 
 class _TorchNet:
@@ -282,12 +322,7 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
         assert (self.trunk.use_hs, self.trunk.setype) == (False, 'avg')
         assert (self.head_pi.use_hs, self.head_pi.setype) == (True, 'max') and (self.head_v.use_hs, self.head_v.setype) == (True, 'max')
         assert self.C == 56 and self.A == 81
-        d, f = self.device, torch.float32
-
-        def pad(t, shape):
-            out = torch.zeros(shape, dtype=f, device=d)
-            out[tuple(slice(0, n) for n in t.shape)] = t
-            return out.contiguous()
+        d, f, pad = self.device, torch.float32, _pad
 
         def flat60(Wf, ncols):        # [7*56][N] (k = l*56 + c) -> [432][ncols] (k = l*60 + c)
             N = Wf.shape[1]
@@ -301,19 +336,9 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
         self._net_keep = first + self.trunk._keep + self.head_pi._keep + self.head_v._keep + head
         assert len(self._net_keep) == 43
         self.net_ptrs = (C.c_void_p * 43)(*[t.data_ptr() for t in self._net_keep])
-
-        def split_frag(Wp):                # zero-padded [K][N], K % 32 == 0 -> [N/16 tiles][K/32 chunks][3 planes hi, mid, lo][64 lanes][8] bf16
-            K, N = Wp.shape
-            m = Wp.contiguous().float()
-            hi = m.to(torch.bfloat16)
-            r1 = m - hi.float()
-            mid = r1.to(torch.bfloat16)
-            lo = (r1 - mid.float()).to(torch.bfloat16)
-            pl = torch.stack([hi, mid, lo]).view(3, K // 32, 4, 8, N // 16, 16)           # plane, chunk, g, j, tile, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                     # tile, chunk, plane, g, r, j
         keep = list(self._net_keep)
         for bi, blk in enumerate((self.trunk, self.head_pi, self.head_v)):
-            keep[2 + 11 * bi] = split_frag(blk.pWe)              # [64][176] (K 56 -> 64 zero padded)
+            keep[2 + 11 * bi] = _split_frag(blk.pWe, 'bf16x3')   # [64][176] (K 56 -> 64 zero padded)
         self._net_keep_split = keep
         self.net_ptrs_split = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
         self._h2_ptrs()
@@ -321,23 +346,11 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
     def _h2_ptrs(self):
         """pointer table + descale factors of azg_nn_v80_forward_h2 (include/azg.h): every matrix zero padded to K % 32 == 0,
         N % 16 == 0, scaled by 2^k (max |w| * 2^k in (2^11, 2^12]) and split into f16 hi / lo fragments"""
-        import math
-        d, f = self.device, torch.float32
-
-        def pad(t, shape):
-            out = torch.zeros(shape, dtype=f, device=d)
-            out[tuple(slice(0, n) for n in t.shape)] = t
-            return out.contiguous()
+        d, f, pad = self.device, torch.float32, _pad
 
         def frag(W, K, N):
-            m = pad(W.to(f), (K, N))
-            k = 12 - int(math.ceil(math.log2(max(float(m.abs().max()), 1e-30))))      # (an all-zero matrix: any scale)
-            m = m * (2.0 ** k)
-            hi = m.to(torch.float16)
-            lo = (m - hi.float()).to(torch.float16)
-            assert bool(torch.isfinite(hi.float()).all())
-            pl = torch.stack([hi, lo]).view(2, K // 32, 4, 8, N // 16, 16)                 # plane, chunk, g, j, tile, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1), (2.0 ** -k) / 64.0   # tile, chunk, plane, g, r, j
+            k = _pow2_scale(W.abs().max())
+            return _split_frag(pad(W, (K, N)), 'h2', k), _descale(k)
 
         def flat64(Wf, N):            # [7*56][N] (k = l*56 + c) -> [448][N] (k = l*64 + c)
             out = torch.zeros((448, Wf.shape[1]), dtype=f, device=d)
@@ -638,21 +651,13 @@ class MobileNet1dHip(_EngineNet):
         self._fused_keep = keep
         self.fused_ptrs = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
         # azg_nn_mb1d_forward_h2: the same table with the matrices as f16 x 2 fragments (K padded to multiples of 32)
-        import math
         r32 = lambda n: (r16(n) + 31) // 32 * 32  # noqa: E731
         desc = []
 
         def fh(W):
-            m = padw(W, r32(W.shape[0]), r16(W.shape[1]))
-            K, N = m.shape
-            k = 12 - int(math.ceil(math.log2(max(float(m.abs().max()), 1e-30))))
-            m = m * (2.0 ** k)
-            hi = m.to(torch.float16)
-            lo = (m - hi.float()).to(torch.float16)
-            assert bool(torch.isfinite(hi.float()).all())
-            desc.append((2.0 ** -k) / 64.0)
-            pl = torch.stack([hi, lo]).view(2, K // 32, 4, 8, N // 16, 16)                # plane, chunk, g, j, tile, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                      # tile, chunk, plane, g, r, j
+            k = _pow2_scale(W.abs().max())
+            desc.append(_descale(k))
+            return _split_frag(padw(W, r32(W.shape[0]), r16(W.shape[1])), 'h2', k)
 
         def flat_rows(W, cout):
             w = torch.zeros((L, OS, W.shape[1]), dtype=torch.float32, device=W.device)
@@ -800,7 +805,6 @@ class SantoriniV89Hip(_EngineNet):
         """h2 (default): the trunk convolutions on f16 x 2 split-precision operands (azg_nn_conv5_forward_h2: three f16 MFMAs per
         product, 22-bit operands, same 1e-5 contract).  Otherwise split: bf16 x 3 (azg_nn_conv5_forward_split, six MFMAs per
         product); False = the f32-MFMA kernel"""
-        import math
         from . import _lib
         self._lib, self.base, self.device, self.split, self.h2 = _lib, base, base.device, bool(split), bool(h2)
         self.P, self.A = base.P, base.A
@@ -808,16 +812,12 @@ class SantoriniV89Hip(_EngineNet):
         frag = SplendorV80Hip._frag
         d = self.device
 
-        def conv_split(w):                 # [co][ci][3][3] -> [4 ct][18 chunks][3 planes][64 lanes][8] bf16
+        def conv_rows(w):                  # [co][ci][3][3] -> [K = tap*64 + ci][co]
             co, ci = w.shape[0], w.shape[1]
-            m = w.permute(2, 3, 1, 0).reshape(9 * ci, co).contiguous().float()          # [K = tap*64 + ci][co]
-            hi = m.to(torch.bfloat16)
-            r1 = m - hi.float()
-            mid = r1.to(torch.bfloat16)
-            lo = (r1 - mid.float()).to(torch.bfloat16)
-            pl = torch.stack([hi, mid, lo])                                               # [3][K][co]
-            pl = pl.view(3, 18, 4, 8, 4, 16)                                              # plane, chunk, g, j, ct, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                     # ct, chunk, plane, g, r, j
+            return w.permute(2, 3, 1, 0).reshape(9 * ci, co)
+
+        def conv_split(w):                 # -> [4 ct][18 chunks][3 planes hi, mid, lo][64 lanes][8] bf16
+            return _split_frag(conv_rows(w), 'bf16x3')
 
         def conv_mat(w, cin_pad):          # [co][ci][3][3] -> [tap*cin_pad + ci][co], fragment order
             co, ci = w.shape[0], w.shape[1]
@@ -825,17 +825,11 @@ class SantoriniV89Hip(_EngineNet):
             m[:, :ci] = w.permute(2, 3, 1, 0).reshape(9, ci, co)
             return frag(m.reshape(9 * cin_pad, co).contiguous())
         convs = [c for blk in base.blocks for c in blk]
-        wmax = max(float(w.abs().max()) for w, _ in convs)
-        k2 = 12 - int(math.ceil(math.log2(max(wmax, 1e-30))))               # one power-of-two scale for the whole trunk: max |w| * 2^k in [2^11, 2^12]
-        self.descale = (2.0 ** -k2) / 64.0
+        k2 = _pow2_scale(max(float(w.abs().max()) for w, _ in convs))       # one power-of-two scale for the whole trunk
+        self.descale = _descale(k2)
 
-        def conv_h2(w):                    # [co][ci][3][3] -> [4 ct][18 chunks][2 planes hi, lo][64 lanes][8] f16 of W * 2^k
-            co, ci = w.shape[0], w.shape[1]
-            m = w.permute(2, 3, 1, 0).reshape(9 * ci, co).contiguous().float() * (2.0 ** k2)
-            hi = m.to(torch.float16)
-            lo = (m - hi.float()).to(torch.float16)
-            pl = torch.stack([hi, lo]).view(2, 18, 4, 8, 4, 16)                          # plane, chunk, g, j, ct, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                     # ct, chunk, plane, g, r, j
+        def conv_h2(w):                    # -> [4 ct][18 chunks][2 planes hi, lo][64 lanes][8] f16 of W * 2^k
+            return _split_frag(conv_rows(w), 'h2', k2)
         keep = [conv_mat(base.c0[0], 16), base.c0[1].contiguous(),
                 torch.cat([(conv_h2(w) if self.h2 else conv_split(w) if self.split else conv_mat(w, 64)) for w, _ in convs]).contiguous(),
                 torch.cat([b for _, b in convs]).contiguous(),
@@ -916,38 +910,25 @@ class SantoriniV78Hip(SantoriniV89Hip):
     csrc/nn_conv5x5.hip.h): one launch for the trunk (MFMA GEMMs for the 1x1 convolutions, in-place depthwise 3x3 on the LDS
     tile) and the value head, one for the 132 x 1782 policy FC (MFMA, 16 samples per workgroup) + masked softmax.  Wraps a SantoriniV78."""
 
-    def __init__(self, base, max_batch=4096, split=True, h2=True):
+    def __init__(self, base, max_batch=4096, split=True, h2=True, policy2=True):
         """h2 (default): the 1x1 convolutions of the trunk and the depthwise pass on f16 x 2 split-precision operands
         (azg_nn_s78_forward_h2: three MFMAs per product).  Otherwise split: bf16 x 3 (azg_nn_s78_forward_split, 8 samples per
-        workgroup, the expanded tile in thirds); False = the f32-MFMA kernel (4 samples per workgroup)"""
-        import math
+        workgroup, the expanded tile in thirds); False = the f32-MFMA kernel (4 samples per workgroup).
+        policy2 (with h2; default): the policy FC as a GEMM launch into the net's own logits workspace + a softmax launch; False = FC +
+        softmax in one launch (k_s78_policy_h2, no workspace)"""
         from . import _lib
         self._lib, self.base, self.device, self.split, self.h2 = _lib, base, base.device, bool(split) or bool(h2), bool(h2)
+        self.policy2 = self.h2 and bool(policy2)
         self.P, self.A = base.P, base.A
         assert base.dtype == torch.float32 and self.device.type == 'cuda' and len(base.blocks) == 10 and self.A == 1782 and self.P == 2
-        ke = 12 - int(math.ceil(math.log2(max(1e-30, max(float(we.abs().max()) for (we, _), _, _ in base.blocks)))))
-        kp = 12 - int(math.ceil(math.log2(max(1e-30, max(float(wp.abs().max()) for _, _, (wp, _) in base.blocks)))))
-        self.ds_e, self.ds_p = (2.0 ** -ke) / 64.0, (2.0 ** -kp) / 64.0
+        ke = _pow2_scale(max(float(we.abs().max()) for (we, _), _, _ in base.blocks))
+        kp = _pow2_scale(max(float(wp.abs().max()) for _, _, (wp, _) in base.blocks))
+        self.ds_e, self.ds_p = _descale(ke), _descale(kp)
 
-        def h2_64(m, k):                   # [64 K][64 N] f32 -> [4 ct][2 chunks of 32][2 planes hi, lo][64 lanes][8] f16 of W * 2^k
-            m = m.contiguous().float() * (2.0 ** k)
-            hi = m.to(torch.float16)
-            lo = (m - hi.float()).to(torch.float16)
-            pl = torch.stack([hi, lo]).view(2, 2, 4, 8, 4, 16)                            # plane, chunk, g, j, ct, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                     # ct, chunk, plane, g, r, j
-
-        def split64(m):                    # [64 K][64 N] f32 -> [4 ct][2 chunks of 32][3 planes hi, mid, lo][64 lanes][8] bf16
-            m = m.contiguous().float()
-            hi = m.to(torch.bfloat16)
-            r1 = m - hi.float()
-            mid = r1.to(torch.bfloat16)
-            lo = (r1 - mid.float()).to(torch.bfloat16)
-            pl = torch.stack([hi, mid, lo]).view(3, 2, 4, 8, 4, 16)                       # plane, chunk, g, j, ct, r
-            return pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1)                     # ct, chunk, plane, g, r, j
-
-        def thirds(ms, of_k):              # the three 64 x 64 pieces of each [64][192] expand / [192][64] project matrix
-            pack = (lambda m: h2_64(m, kp if of_k else ke)) if self.h2 else split64
-            return torch.cat([pack(m[64 * t:64 * t + 64] if of_k else m[:, 64 * t:64 * t + 64]) for m in ms for t in range(3)]).contiguous()
+        def thirds(ms, of_k):              # the three 64 x 64 pieces of each [64][192] expand / [192][64] project matrix, each
+            # [4 ct][2 chunks of 32][planes][64 lanes][8]: f16 hi / lo of W * 2^k (h2) or bf16 hi / mid / lo
+            kind, k = ('h2', kp if of_k else ke) if self.h2 else ('bf16x3', 0)
+            return torch.cat([_split_frag(m[64 * t:64 * t + 64] if of_k else m[:, 64 * t:64 * t + 64], kind, k) for m in ms for t in range(3)]).contiguous()
         frag = SplendorV80Hip._frag
         d = self.device
         m0 = torch.zeros((9, 16, 64), dtype=torch.float32, device=d)
@@ -959,15 +940,9 @@ class SantoriniV78Hip(SantoriniV89Hip):
         bfp = torch.zeros(1792, dtype=torch.float32, device=d)
         bfp[:1782] = base.fc_pi[1]
         if self.h2:                        # the policy FC on f16 x 2 operands too (k_s78_policy_h2): K 132 -> 160, hi / lo fragments + the descale
-            kf = 12 - int(math.ceil(math.log2(max(1e-30, float(base.fc_pi[0].abs().max())))))
-            m = torch.zeros((160, 1792), dtype=torch.float32, device=d)
-            m[:132, :1782] = base.fc_pi[0]
-            m *= 2.0 ** kf
-            hi = m.to(torch.float16)
-            lo = (m - hi.float()).to(torch.float16)
-            pl = torch.stack([hi, lo]).view(2, 5, 4, 8, 112, 16)                          # plane, chunk, g, j, ct, r
-            fr = pl.permute(4, 1, 0, 2, 5, 3).contiguous().view(-1).view(torch.uint8)     # ct, chunk, plane, g, r, j
-            tail = torch.tensor([(2.0 ** -kf) / 64.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=d).view(torch.uint8)
+            kf = _pow2_scale(base.fc_pi[0].abs().max())
+            fr = _split_frag(_pad(base.fc_pi[0], (160, 1792)), 'h2', kf).view(torch.uint8)
+            tail = torch.tensor([_descale(kf), 0.0, 0.0, 0.0], dtype=torch.float32, device=d).view(torch.uint8)
             wfp_h2 = torch.cat([fr, tail]).contiguous()
         keep = [frag(m0.reshape(144, 64).contiguous()),
                 (thirds([we.reshape(192, 64).t() for (we, _), _, _ in base.blocks], False) if self.split else
@@ -984,11 +959,16 @@ class SantoriniV78Hip(SantoriniV89Hip):
         self.ptrs = (C.c_void_p * 19)(*[t.data_ptr() for t in keep])
         self._alloc(max_batch)
 
+    def _alloc(self, B):
+        super()._alloc(B)
+        if self.policy2:               # the raw logits between the policy GEMM and the softmax: an activation buffer like pi and v
+            self.logits = torch.empty((B, 1792), dtype=torch.float32, device=self.device)
+
     def _launch(self, boards, valids, B, stream):
         L = self._lib.lib()
         if self.h2:
             self._lib.check(L.azg_nn_s78_forward_h2(boards, valids, self.ptrs, self.ds_e, self.ds_p, 10, self.A, self.P, B, _ptr(self.pi),
-                                                    _ptr(self.v), stream))
+                                                    _ptr(self.v), _ptr(self.logits) if self.policy2 else None, stream))
             return
         fwd = L.azg_nn_s78_forward_split if self.split else L.azg_nn_s78_forward
         self._lib.check(fwd(boards, valids, self.ptrs, 10, self.A, self.P, B, _ptr(self.pi), _ptr(self.v), stream))
