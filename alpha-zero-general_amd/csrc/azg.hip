@@ -94,7 +94,7 @@ extern "C" int azg_env_init_boards(int game, int variant, int n, int8_t* out_sta
     if (n <= 0) return 0;
     variant = norm_variant(game, variant);
     AZG_DISPATCH(game, variant, k_env_init_boards<G><<<dim3(n), dim3(64), 0, (hipStream_t)stream>>>(n,
-                                                    out_states, rng_seed, stream0, out_counters));
+                                                    out_states, rng_seed, stream0, out_counters, variant));
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -316,6 +316,7 @@ extern "C" int azg_forest_create(const azg_forest_cfg* cfg, azg_forest** out) {
     ForestDev& D = f->dev;
     memset(&D, 0, sizeof(D));
     D.T = cfg->n_trees;
+    D.variant = variant;
     D.cap = cfg->node_capacity;
     int ht = 64;
     while (ht < 2 * D.cap) ht <<= 1;

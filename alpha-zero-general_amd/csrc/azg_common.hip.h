@@ -181,4 +181,10 @@ template <int N> struct RoundUp16 { static constexpr int value = (N + 15) / 16 *
 template <class G, class = void> struct MoveScratch { static constexpr int value = 0; };
 template <class G> struct MoveScratch<G, std::void_t<decltype(G::MOVE_SCRATCH)>> { static constexpr int value = G::MOVE_SCRATCH; };
 
+// Board.init_game (G::init_board, lane 0 on a zeroed state) of a game whose starting position depends on a part of the variant that no kernel is
+// compiled for (G::INIT_TAKES_VARIANT: Abalone's layout) takes the normalised variant as a third argument.  The two callers choose with
+// `if constexpr` on this trait at the call itself, so that the call of every other game compiles exactly as before.
+template <class G, class = void> struct InitTakesVariant { static constexpr bool value = false; };
+template <class G> struct InitTakesVariant<G, std::void_t<decltype(G::INIT_TAKES_VARIANT)>> { static constexpr bool value = G::INIT_TAKES_VARIANT; };
+
 }  // namespace azg

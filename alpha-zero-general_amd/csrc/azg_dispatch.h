@@ -22,7 +22,8 @@
         else if ((game) == AZG_SANTORINI && (variant) == 1) { using G = SantoriniDev<1>; __VA_ARGS__; }   \
         else if ((game) == AZG_SANTORINI && (variant) == 11) { using G = SantoriniDev<11>; __VA_ARGS__; } \
         else if ((game) == AZG_AZUL) { using G = AzulDev; __VA_ARGS__; }                                   \
-        else if ((game) == AZG_ABALONE) { using G = AbaloneDev; __VA_ARGS__; }                             \
+        else if ((game) == AZG_ABALONE && (variant) >= 1 && (variant) <= 3) { using G = AbaloneDevT<false>; __VA_ARGS__; } \
+        else if ((game) == AZG_ABALONE && (variant) >= 5 && (variant) <= 7) { using G = AbaloneDevT<true>; __VA_ARGS__; }  \
         else if ((game) == AZG_MINIVILLES && (variant) == 2) { using G = MinivillesDev<2>; __VA_ARGS__; } \
         else if ((game) == AZG_MINIVILLES && (variant) == 3) { using G = MinivillesDev<3>; __VA_ARGS__; } \
         else if ((game) == AZG_MINIVILLES && (variant) == 4) { using G = MinivillesDev<4>; __VA_ARGS__; } \
@@ -44,7 +45,8 @@ static inline int norm_variant(int game, int variant) {
     if (game == AZG_SANTORINI) return variant ? variant : 11;
     if (game == AZG_AZUL) return 2;
     if (game == AZG_MINIVILLES) return variant ? variant : 2;
-    if (game == AZG_ABALONE) return 1;
+    if (game == AZG_ABALONE)        // bits 0-1 the layout (0 = the default, Belgian Daisy), bit 2 dynamic komi; anything else is refused
+        return (variant & ~7) ? -1 : ((variant & 3) ? variant : (variant | 1));
     if (game == AZG_TLP) return variant ? variant : 3;
     if (game == AZG_BOTANIK) return 2;
     if (game == AZG_AKROPOLIS) return variant ? variant : 2;

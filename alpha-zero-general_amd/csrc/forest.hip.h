@@ -111,6 +111,7 @@ struct PathEnt {
 struct ForestDev {
     int T, cap, HT, U;                 // trees, nodes per tree, hash slots per tree (pow2), child slots per action
     uint32_t heap_units;               // 16-byte units per tree heap
+    int variant;                       // the game's normalised variant, for the part of it that is no template argument (InitTakesVariant)
     // per-tree strides: the sizes rounded up to an ODD multiple of 256 B, so that "the same offset in every tree" (root
     // record, node 0, ...) walks over all HBM channels instead of hitting one (power-of-two strides were ~8 % slower)
     size_t s_heap, s_nstate;           // bytes

@@ -1,8 +1,17 @@
 // game_abalone.hip.h -- Abalone env step on the device plugin interface: abalone/AbaloneLogicNumba.py
-// (Board :166-440) as shipped: INITIAL_LAYOUT = 1 (Belgian Daisy), ENABLE_DYNAMIC_KOMI = False (:5-6).
+// (Board :166-440) for every value of its two module constants (:5-6): INITIAL_LAYOUT 0 / 1 / 2 (classic / Belgian Daisy / German
+// Daisy; 1 is the shipped value) and ENABLE_DYNAMIC_KOMI (shipped False).
+//
+// The layout matters to init_game alone, so it is a run-time argument of init_board (the C-ABI variant, include/azg.h) and costs no
+// kernel.  Dynamic komi touches init_game (one random bit in misc[0][3]), check_end_game (the bit decides a score tie at the round
+// limit; no 0.001 draw) and swap_players (an odd swap flips the bit): AbaloneDevT<KOMI> compiles each of the three once per flag, so
+// a kernel exists twice for Abalone, not six times.  valid_moves, make_move and the symmetries never look at the bit (the misc plane
+// is copied untransformed).  The bit is one of the state bytes (byte 15), so node hashing, transpositions and edge memoisation need
+// nothing new: a position with the other bit is another node.
 //
 // State int8 [9][9][4] on an axial hex grid (playable cells: 4 <= r + q <= 12): plane 0 marbles of player 0, plane 1 of player 1,
-// plane 2 the board mask, plane 3 misc with misc[0][0..2] = the two scores and the move counter; byte = (r*9 + q)*4 + plane.
+// plane 2 the board mask, plane 3 misc with misc[0][0..2] = the two scores and the move counter and, with komi, misc[0][3] = 1 when
+// player 0 wins a tie; byte = (r*9 + q)*4 + plane.
 // 3402 actions = anchor cell x 42 planes: one marble in direction d (6), two / three marbles along `axis` moved in direction d
 // (3 x 6 each), the anchor being the marble with the smallest (r, q) (:66-88).  Deterministic: make_move ignores random_seed, so
 // a resolved edge is memoised in every universe slot.
@@ -14,7 +23,11 @@
 
 namespace azg {
 
-struct AbaloneDev {
+// variant (after norm_variant): bits 0-1 the layout, bit 2 dynamic komi
+enum { ABA_BELGIAN = 1, ABA_GERMAN = 2, ABA_CLASSIC = 3, ABA_KOMI = 4 };
+
+template <bool KOMI>
+struct AbaloneDevT {
     static constexpr int P = 2;
     static constexpr int ROWS = 81, COLS = 4;
     static constexpr int S = 324;
@@ -116,7 +129,7 @@ struct AbaloneDev {
 
     __device__ static __forceinline__ bool move_uses_seed(int) { return false; }
     __device__ static __forceinline__ int wave_make_move(int8_t* st, int move, int player, long long seed, Rng& rng) {
-        return lane0_make_move<AbaloneDev>(st, move, player, seed, rng);
+        return lane0_make_move<AbaloneDevT<KOMI>>(st, move, player, seed, rng);
     }
     // Board.make_move :358-396 -- lane 0 only
     __device__ static int make_move(int8_t* st, int move, int player, long long seed, Rng& rng) {
@@ -152,7 +165,7 @@ struct AbaloneDev {
     __device__ static __forceinline__ int get_score(const int8_t* st, int p) { return cell(st, 0, p == 0 ? 0 : 1, 3); }   // :265-266
     __device__ static __forceinline__ int gc_age(const int8_t* st) { return (int)(uint8_t)cell(st, 0, 2, 3); }            // every move adds 1
 
-    // Board.check_end_game :398-413 (uniform)
+    // Board.check_end_game :376-392 (uniform)
     __device__ static bool game_ended(const int8_t* st, int next_player, float* out, uint64_t* mask_scratch) {
         (void)next_player; (void)mask_scratch;
         const int s0 = cell(st, 0, 0, 3), s1 = cell(st, 0, 1, 3);
@@ -162,36 +175,63 @@ struct AbaloneDev {
         if (cell(st, 0, 2, 3) >= 127) {
             if (s0 > s1) { out[0] = 1.f; out[1] = -1.f; }
             else if (s1 > s0) { out[0] = -1.f; out[1] = 1.f; }
+            else if (KOMI) { out[0] = cell(st, 0, 3, 3) == 1 ? 1.f : -1.f; out[1] = -out[0]; }                            // :385-389
             else { out[0] = out[1] = 0.001f; }
             return true;
         }
         return false;
     }
 
-    // Board.swap_players :415-426 -- wave-cooperative: the two marble planes and the two scores trade places
+    // Board.swap_players :394-406 -- wave-cooperative: the two marble planes and the two scores trade places; the komi bit flips
     __device__ static void swap_players(int8_t* st, int8_t* tmp, int k) {
         (void)tmp;
         if (k % 2 != 1) return;
         for (int c = lane_id(); c < 81; c += 64) { const int8_t t = st[4 * c]; st[4 * c] = st[4 * c + 1]; st[4 * c + 1] = t; }
         wave_sync();
-        if (lane_id() == 0) { const int8_t t = st[3]; st[3] = st[7]; st[7] = t; }
+        if (lane_id() == 0) {
+            const int8_t t = st[3]; st[3] = st[7]; st[7] = t;
+            if (KOMI) st[15] = (int8_t)(1 - st[15]);
+        }
         wave_sync();
     }
 
-    // init_game :175-222 (layout 1) -- lane 0; state zeroed by the caller
-    __device__ static void init_board(int8_t* st, Rng& rng) {
-        (void)rng;
+    // init_game :167-233 -- lane 0; state zeroed by the caller.  `variant`: the layout in bits 0-1 (ABA_*).  With komi the bit is
+    // floor(2 u) of ONE uniform (np.random.randint(2), :233); without it nothing is drawn.
+    // A layout is the set of cells c = r * 9 + q that hold a marble of player 0 / of the opponent, as bits (lo: cells 0..63, hi: 64..80),
+    // made at compile time from the rows of :179-227, so that choosing one at run time is a select between constants (three blocks of
+    // constant stores, one per layout, cost the self-play kernels more scalar registers than this).
+    struct Marbles { uint64_t lo[2]; uint32_t hi[2]; };
+    static constexpr Marbles marbles(int layout) {
+        // six rows each: [q_lo, q_hi) of player 0's and of the opponent's marbles
+        constexpr int rows[3][6] = {{0, 1, 2, 6, 7, 8}, {0, 1, 2, 6, 7, 8}, {1, 2, 3, 5, 6, 7}};           // classic, Belgian, German
+        constexpr int mlo[3][6] = {{0, 0, 0, 2, 0, 0}, {7, 6, 6, 1, 0, 0}, {6, 5, 5, 2, 1, 1}};
+        constexpr int mhi[3][6] = {{0, 0, 0, 5, 6, 5}, {9, 9, 8, 3, 3, 2}, {8, 8, 7, 4, 4, 3}};
+        constexpr int olo[3][6] = {{4, 3, 4, 0, 0, 0}, {4, 3, 3, 4, 3, 3}, {4, 3, 3, 4, 3, 3}};
+        constexpr int ohi[3][6] = {{9, 9, 7, 0, 0, 0}, {6, 6, 5, 6, 6, 5}, {6, 6, 5, 6, 6, 5}};
+        Marbles m{{0, 0}, {0, 0}};
+        for (int i = 0; i < 6; i++)
+            for (int z = 0; z < 2; z++)
+                for (int q = z ? olo[layout][i] : mlo[layout][i]; q < (z ? ohi[layout][i] : mhi[layout][i]); q++) {
+                    const int c = rows[layout][i] * 9 + q;
+                    if (c < 64) m.lo[z] |= 1ull << c; else m.hi[z] |= 1u << (c - 64);
+                }
+        return m;
+    }
+    static constexpr bool INIT_TAKES_VARIANT = true;
+    __device__ static void init_board(int8_t* st, Rng& rng, int variant) {
+        constexpr Marbles C = marbles(0), B = marbles(1), G = marbles(2);
+        const int layout = variant & 3;
+        const bool cl = layout == ABA_CLASSIC, ge = layout == ABA_GERMAN;
+        const uint64_t lo0 = cl ? C.lo[0] : (ge ? G.lo[0] : B.lo[0]), lo1 = cl ? C.lo[1] : (ge ? G.lo[1] : B.lo[1]);
+        const uint32_t hi0 = cl ? C.hi[0] : (ge ? G.hi[0] : B.hi[0]), hi1 = cl ? C.hi[1] : (ge ? G.hi[1] : B.hi[1]);
         for (int r = 0; r < 9; r++)
-            for (int q = 0; q < 9; q++)
+            for (int q = 0; q < 9; q++) {
+                const int c = r * 9 + q;
                 if (r + q >= 4 && r + q <= 12) cellw(st, r, q, 2) = 1;
-        // rows {0, 1, 2, 6, 7, 8}: [q_lo, q_hi) of the opponent's and of player 0's marbles
-        const int rows[6] = {0, 1, 2, 6, 7, 8};
-        const int olo[6] = {4, 3, 3, 4, 3, 3}, ohi[6] = {6, 6, 5, 6, 6, 5};
-        const int mlo[6] = {7, 6, 6, 1, 0, 0}, mhi[6] = {9, 9, 8, 3, 3, 2};
-        for (int i = 0; i < 6; i++) {
-            for (int q = olo[i]; q < ohi[i]; q++) cellw(st, rows[i], q, 1) = 1;
-            for (int q = mlo[i]; q < mhi[i]; q++) cellw(st, rows[i], q, 0) = 1;
-        }
+                cellw(st, r, q, 0) = (int8_t)(c < 64 ? (lo0 >> c) & 1 : (hi0 >> (c - 64)) & 1);
+                cellw(st, r, q, 1) = (int8_t)(c < 64 ? (lo1 >> c) & 1 : (hi1 >> (c - 64)) & 1);
+            }
+        if (KOMI) cellw(st, 0, 3, 3) = (int8_t)(int)(2.0 * rng.u01());
     }
 
     // ---- get_symmetries :428-460: 6 rotations x 2 flips (always 12 forms, identity first) ----
@@ -237,5 +277,6 @@ struct AbaloneDev {
         return encode(mr[mi], mq[mi], x.size, axis, d);
     }
 };
+using AbaloneDev = AbaloneDevT<false>;
 
 }  // namespace azg

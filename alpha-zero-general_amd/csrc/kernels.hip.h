@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64) void k_env_symmetries_built(const int8_t* state
 
 template <class G>
 __global__ __launch_bounds__(64) void k_env_init_boards(int n, int8_t* out_states, uint64_t rng_seed, uint64_t stream0,
-                                                        uint64_t* out_counters) {
+                                                        uint64_t* out_counters, int variant) {
     __shared__ __attribute__((aligned(16))) int8_t st[G::SP];
     int t = blockIdx.x;
     if (t >= n) return;
@@ -161,7 +161,8 @@ __global__ __launch_bounds__(64) void k_env_init_boards(int n, int8_t* out_state
     wave_sync();
     if (lane_id() == 0) {
         Rng rng{rng_seed, stream0 + (uint64_t)t, 0ull};
-        G::init_board(st, rng);
+        if constexpr (InitTakesVariant<G>::value) G::init_board(st, rng, variant);
+        else G::init_board(st, rng);
         if (out_counters) out_counters[t] = rng.counter;
     }
     wave_sync();

@@ -119,7 +119,10 @@ __device__ void start_game(const ForestDev& F, int t, TreeHdr& H, typename Fores
     else {
         for (int i = lane_id(); i < G::SP; i += 64) sm.st[i] = 0;
         wave_sync();
-        if (lane_id() == 0) G::init_board(sm.st, rng);
+        if (lane_id() == 0) {
+            if constexpr (InitTakesVariant<G>::value) G::init_board(sm.st, rng, F.variant);
+            else G::init_board(sm.st, rng);
+        }
         rng.counter = bcast_u64(rng.counter, 0);
         wave_sync();
     }

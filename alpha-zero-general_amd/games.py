@@ -229,12 +229,34 @@ class MinivillesGame(HipGame):
         super().__init__(num_players, **kw)
 
 
+ABALONE_LAYOUTS = ('classic', 'belgian', 'german')       # the reference's INITIAL_LAYOUT 0 / 1 / 2 (abalone/AbaloneLogicNumba.py:5)
+
+
+def abalone_variant(layout='belgian', dynamic_komi=False):
+    """(layout name or the reference's integer, ENABLE_DYNAMIC_KOMI) -> (layout name, bool, the C-ABI variant of include/azg.h: bits 0-1
+    the layout -- 1 Belgian Daisy, 2 German Daisy, 3 classic -- and 4 for dynamic komi).  ValueError for anything else."""
+    if isinstance(layout, str):
+        name = layout.lower()
+    elif isinstance(layout, (int, np.integer)) and not isinstance(layout, bool) and 0 <= layout < len(ABALONE_LAYOUTS):
+        name = ABALONE_LAYOUTS[layout]
+    else:
+        name = None
+    if name not in ABALONE_LAYOUTS:
+        raise ValueError('Abalone layout %r: one of %s or 0 / 1 / 2' % (layout, ' / '.join(map(repr, ABALONE_LAYOUTS))))
+    if not isinstance(dynamic_komi, (bool, np.bool_)):
+        raise ValueError('Abalone dynamic_komi %r: True or False' % (dynamic_komi,))
+    return name, bool(dynamic_komi), {'belgian': 1, 'german': 2, 'classic': 3}[name] | (4 if dynamic_komi else 0)
+
+
 class AbaloneGame(HipGame):
-    """abalone/AbaloneGame.py (2 players, Belgian-Daisy layout, no dynamic komi: the shipped constants)"""
+    """abalone/AbaloneGame.py (2 players) for every value of the reference's two module constants (abalone/AbaloneLogicNumba.py:5-6):
+    layout 'classic' | 'belgian' | 'german' (or its INITIAL_LAYOUT 0 / 1 / 2) and dynamic_komi (ENABLE_DYNAMIC_KOMI: getInitBoard draws
+    who wins a score tie at the round limit into misc[0, 3], and there is no 0.001 draw).  The defaults are the shipped constants."""
     GAME_ID = _lib.ABALONE
 
-    def __init__(self, **kw):
-        super().__init__(1, **kw)
+    def __init__(self, layout='belgian', dynamic_komi=False, **kw):
+        self.layout, self.dynamic_komi, variant = abalone_variant(layout, dynamic_komi)
+        super().__init__(variant, **kw)
 
 
 class TLPGame(HipGame):

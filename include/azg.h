@@ -45,7 +45,9 @@ int azg_set_device(int device);
 /* GameSwitcher.import_game + Game.getBoardSize/getActionSize/getNumberOfPlayers (GameSwitcher.py:15-24, Game.py:27-42).
    variant: Splendor = NUMBER_PLAYERS (2..4, splendor/SplendorGame.py:9); Santorini = NB_GODS (1 or 11,
    santorini/SantoriniConstants.py:19); Azul = 2 players (azul/AzulGame.py:9); Minivilles = NUMBER_PLAYERS (2..4,
-   minivilles/MinivillesGame.py:9); Abalone = 2 players, Belgian-Daisy layout (abalone/AbaloneLogicNumba.py:5); The Little Prince =
+   minivilles/MinivillesGame.py:9); Abalone = the two module constants of abalone/AbaloneLogicNumba.py:5-6 in one word: bits 0-1 the starting layout (0 or
+   1 Belgian Daisy, 2 German Daisy, 3 classic), bit 2 (value 4) ENABLE_DYNAMIC_KOMI -- init draws one uniform u and stores floor(2 u) in
+   misc[0][3], the bit decides a score tie at the round limit and flips with the seats; any other bit is refused; The Little Prince =
    NUMBER_PLAYERS (3..5, thelittleprince/TLPGame.py:9); Botanik = 2 players; Akropolis = N_PLAYERS (2..4,
    akropolis/AkropolisConstants.py:3); Smallworld = NUMBER_PLAYERS (2..4, smallworld/SmallworldConstants.py).  0 = the shipped constant. */
 int azg_game_info(int game, int variant, int* state_bytes, int* action_size, int* num_players, int* rows, int* cols);

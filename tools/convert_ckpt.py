@@ -18,6 +18,9 @@ GOLDEN = os.path.join(HERE, '..', 'tests', 'golden')
 # weightstats_<tag>.npz (shapes and per-tensor statistics, azg_amd.formats.weight_stats) and the forward vectors are the reference
 # module's outputs on the stand-in weights drawn from it (formats.synthetic_state_dict)
 STANDIN = {'minivilles4_v82': 4}
+# tags whose boards do not come from env_<first word of the tag>.npz: the nets of Abalone's two other layouts take the positions of their own
+# layout (tools/gen_golden_abalone_variants.py), the classic one -- trained with dynamic komi -- boards that carry the komi bit
+ENV_OF = {'abalone_v21_german': 'abalone_german', 'abalone_v21_classic': 'abalone_classic_komi'}
 
 
 def _standin(name, model):
@@ -47,7 +50,7 @@ def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True
             out['arg/' + k] = np.array(v)
         elif isinstance(v, (list, tuple)) and all(isinstance(x, (int, float)) for x in v):
             out['arg/' + k] = np.array(v, dtype=np.float64)
-    np.savez_compressed(os.path.join(GOLDEN, '%s_%s.npz' % ('weightstats' if name in STANDIN else 'weights', name)), **out)
+    H.savez(os.path.join(GOLDEN, '%s_%s.npz' % ('weightstats' if name in STANDIN else 'weights', name)), **out)
     print(name, 'args:', {k: v for k, v in meta.items() if k in ('nn_version', 'cpuct', 'fpu', 'universes', 'numMCTSSims',
                                                                    'dirichletAlpha', 'temperature', 'tempThreshold')})
     if not forward:      # the pickled full_model needs the real torchvision (absent here): weights + args only
@@ -58,7 +61,7 @@ def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True
     model = ck['full_model'].eval()
     if name in STANDIN:
         model = _standin(name, model)
-    env = np.load(os.path.join(GOLDEN, 'env_%s.npz' % name.split('_')[0]))
+    env = np.load(os.path.join(GOLDEN, 'env_%s.npz' % ENV_OF.get(name, name.split('_')[0])))
     rng = np.random.default_rng(0)
     sel = rng.choice(len(env['canonical']), size=min(n_vec, len(env['canonical'])), replace=False)
     g = getattr(m[game_mod], game_cls)()
@@ -67,8 +70,8 @@ def convert(name, ckpt_rel, load_kw, game_mod, game_cls, n_vec=256, forward=True
     masks = np.array([g.getValidMoves(b, 0) for b in boards])
     with torch.no_grad():
         lp, v = model(torch.from_numpy(boards.astype(np.float32)), torch.from_numpy(masks.astype(bool)))
-    np.savez_compressed(os.path.join(GOLDEN, 'netfwd_%s.npz' % name), boards=boards.astype(np.int8),
-                        masks=masks.astype(np.uint8), pi=torch.exp(lp).numpy(), v=v.numpy())
+    H.savez(os.path.join(GOLDEN, 'netfwd_%s.npz' % name), boards=boards.astype(np.int8),
+            masks=masks.astype(np.uint8), pi=torch.exp(lp).numpy(), v=v.numpy())
     print('wrote weights +', len(sel), 'forward vectors for', name)
     H.cleanup()
 
@@ -93,7 +96,7 @@ def forward_f64(name, ckpt_rel, load_kw):
     with torch.no_grad():
         lp, v = model(torch.from_numpy(d['boards'].astype(np.float64)), torch.from_numpy(d['masks'].astype(bool)))
     pi64, v64 = torch.exp(lp).numpy(), v.numpy()
-    np.savez_compressed(os.path.join(GOLDEN, 'netfwd64_%s.npz' % name), pi64=pi64, v64=v64)
+    H.savez(os.path.join(GOLDEN, 'netfwd64_%s.npz' % name), pi64=pi64, v64=v64)
     print('%-16s |ref_f32 - ref_f64|: pi %.3g  v %.3g' % (name, np.abs(d['pi'] - pi64).max(), np.abs(d['v'] - v64).max()))
     H.cleanup()
 
@@ -133,6 +136,8 @@ F64 = [('splendor2_v80', 'splendor/pretrained_2players.pt', dict(splendor_player
        ('tlp4_v83', 'thelittleprince/pretrained_4players.pt', dict(tlp_players=4)),
        ('tlp5_v83', 'thelittleprince/pretrained_5players.pt', dict(tlp_players=5)),
        ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict()),
+       ('abalone_v21_german', 'abalone/pretrained_GermanDaisy.pt', dict(abalone_layout=2)),
+       ('abalone_v21_classic', 'abalone/pretrained_classic.pt', dict(abalone_layout=0, abalone_dynamic_komi=True)),
        ('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2)),
        ('smallworld3_v62', 'smallworld/pretrained_3pl.pt', dict(smallworld_players=3)),
        ('smallworld4_v62', 'smallworld/pretrained_4pl.pt', dict(smallworld_players=4)),
@@ -245,6 +250,11 @@ def main():
                          # AbaloneNNet.py nn_version 21 (Belgian Daisy, the layout the engine plays): a 2-d MobileNet on the 9 x 9 grid,
                          # torchvision InvertedResidual blocks (the refshim stand-in); engine net through nn_abalone.hip.h
                          'abalone_v21': ('abalone_v21', 'abalone/pretrained_BelgianDaisy.pt', dict(), 'AbaloneGame', 'AbaloneGame', 128),
+                         # the checkpoints of the two other layouts (the classic one from a dynamic-komi run): same net, same kernel
+                         'abalone_v21_german': ('abalone_v21_german', 'abalone/pretrained_GermanDaisy.pt', dict(abalone_layout=2),
+                                                'AbaloneGame', 'AbaloneGame', 128),
+                         'abalone_v21_classic': ('abalone_v21_classic', 'abalone/pretrained_classic.pt',
+                                                 dict(abalone_layout=0, abalone_dynamic_komi=True), 'AbaloneGame', 'AbaloneGame', 128),
                          # SmallworldNNet.py nn_version 62 (all three shipped checkpoints): a 3-layer transformer encoder over the
                          # (N, 8) tokens; engine net through nn_smallworld.hip.h
                          'smallworld_v62': ('smallworld_v62', 'smallworld/pretrained_2pl.pt', dict(smallworld_players=2), 'SmallworldGame',

@@ -7,7 +7,7 @@ travels to the GPU box as an executable dependency: -m gpu tests, smoke() and be
 What it does (SURVEY.md §8c recipe):
   * puts the stub `numba` / `colorama` / `torchvision` packages of this directory in front of sys.path
     (identity decorators == the reference's NUMBA_DISABLE_JIT=1 debug mode, README.md:169-171);
-  * variants that are source-level constants in the reference (NUMBER_PLAYERS, NB_GODS, INIT_METHOD) are
+  * variants that are source-level constants in the reference (NUMBER_PLAYERS, NB_GODS, INIT_METHOD, Abalone's INITIAL_LAYOUT / ENABLE_DYNAMIC_KOMI) are
     produced by editing a TEMP COPY of the reference tree (never the repo, never /root/reference);
   * patches splendor.SplendorLogicNumba.my_packbits to wrap uint8->int8 like Numba's silent int8 store
     (NumPy 2 raises OverflowError for 255 -> int8); widens azul's np_factory_symmetries table to int64 (Numba widens
@@ -19,10 +19,12 @@ What it does (SURVEY.md §8c recipe):
     value-identical to what the Numba-compiled code computes (minus fastmath reassociation).
 """
 import importlib
+import io
 import os
 import shutil
 import sys
 import tempfile
+import zipfile
 
 import numpy as np
 
@@ -42,7 +44,8 @@ def _purge_modules():
             del sys.modules[name]
 
 
-def load_reference(splendor_players=2, santorini_gods=11, santorini_init_method=1, minivilles_players=2, tlp_players=3, smallworld_players=2, akropolis_players=2):
+def load_reference(splendor_players=2, santorini_gods=11, santorini_init_method=1, minivilles_players=2, tlp_players=3, smallworld_players=2, akropolis_players=2, abalone_layout=1,
+                   abalone_dynamic_komi=False):
     """Import the reference from a temp copy with the requested source-level variants.
     Returns a dict of modules."""
     tmp = tempfile.mkdtemp(prefix='azg_ref_')
@@ -70,6 +73,10 @@ def load_reference(splendor_players=2, santorini_gods=11, santorini_init_method=
     sub('thelittleprince/TLPGame.py', 'NUMBER_PLAYERS = 3', 'NUMBER_PLAYERS = %d' % tlp_players)
     sub('smallworld/SmallworldConstants.py', 'NUMBER_PLAYERS = 2', 'NUMBER_PLAYERS = %d' % smallworld_players)
     sub('akropolis/AkropolisConstants.py', 'N_PLAYERS = 2', 'N_PLAYERS = %d' % akropolis_players)
+    if abalone_layout != 1:
+        sub('abalone/AbaloneLogicNumba.py', 'INITIAL_LAYOUT              = 1', 'INITIAL_LAYOUT              = %d' % abalone_layout)
+    if abalone_dynamic_komi:
+        sub('abalone/AbaloneLogicNumba.py', 'ENABLE_DYNAMIC_KOMI         = False', 'ENABLE_DYNAMIC_KOMI         = True')
 
     _purge_modules()
     sys.dont_write_bytecode = True
@@ -254,6 +261,19 @@ def mcts_args(utils_mod, **kw):
                 tempThreshold=10)
     base.update(kw)
     return utils_mod.dotdict(base)
+
+
+def savez(path, **arrays):
+    """np.savez_compressed with nothing of the moment in the file: the members carry a fixed date instead of the time of writing, so a
+    generator run again writes the same bytes"""
+    with zipfile.ZipFile(path, 'w', zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
 
 
 def cleanup():

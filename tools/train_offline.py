@@ -36,7 +36,7 @@ def build_parser():
     parser.add_argument('--q-weight', '-q', action='store', default=0.5, type=float, help='Weight for mixing Q into value loss')
     # not in the reference, where a game's module constants say this
     parser.add_argument('--num-players', action='store', default=None, type=int, help='Players (splendor, minivilles, thelittleprince, akropolis, smallworld)')
-    parser.add_argument('--variant', action='store', default=None, type=int, help='Santorini: number of gods (1 = no gods, 11)')
+    parser.add_argument('--variant', action='store', default=None, type=int, help='Santorini: number of gods (1 = no gods, 11); Abalone: the variant word of include/azg.h (1 Belgian Daisy, 2 German Daisy, 3 classic, + 4 dynamic komi)')
     return parser
 
 
@@ -48,9 +48,14 @@ def make_game(args):
             raise SystemExit('--num-players: %s has a fixed number of players' % args.game)
         kw['num_players'] = args.num_players
     if args.variant is not None:
-        if args.game != 'santorini':
-            raise SystemExit('--variant is for santorini')
-        kw['nb_gods'] = args.variant
+        if args.game == 'abalone':
+            if not 1 <= args.variant <= 7 or args.variant & 3 == 0:
+                raise SystemExit('--variant: abalone takes 1 / 2 / 3 (Belgian Daisy / German Daisy / classic), + 4 for dynamic komi')
+            kw.update(layout={1: 'belgian', 2: 'german', 3: 'classic'}[args.variant & 3], dynamic_komi=bool(args.variant & 4))
+        elif args.game != 'santorini':
+            raise SystemExit('--variant is for santorini and abalone')
+        else:
+            kw['nb_gods'] = args.variant
     return games.import_game(args.game, **kw)
 
 
