@@ -39,8 +39,8 @@ EXPORTS = [
     'azg_forest_destroy', 'azg_forest_device_bytes', 'azg_forest_reset', 'azg_forest_begin_search',
     'azg_forest_select', 'azg_forest_select_fused', 'azg_forest_rounds_v80_h2', 'azg_forest_rounds_profile', 'azg_forest_expand_backup', 'azg_forest_active', 'azg_forest_action_probs',
     'azg_forest_root_stats', 'azg_forest_dump_tree', 'azg_forest_validate', 'azg_selfplay_start', 'azg_selfplay_start_ex', 'azg_selfplay_advance', 'azg_selfplay_active',
-    'azg_selfplay_stats_get', 'azg_selfplay_drain_examples', 'azg_forest_last_kernel_ms', 'azg_forest_enable_timing', 'azg_forest_set_search_params', 'azg_nn_linear', 'azg_nn_linear_ws', 'azg_nn_dw_pool', 'azg_nn_v80_block', 'azg_nn_v80_forward', 'azg_nn_v80_forward_split', 'azg_nn_v80_forward_h2',
-    'azg_nn_board_to_x', 'azg_nn_heads_out', 'azg_nn_dw_pool_l', 'azg_nn_board_to_x_ld', 'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
+    'azg_selfplay_stats_get', 'azg_selfplay_drain_examples', 'azg_forest_last_kernel_ms', 'azg_forest_enable_timing', 'azg_forest_set_search_params', 'azg_nn_v80_forward', 'azg_nn_v80_forward_split', 'azg_nn_v80_forward_h2',
+    'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
     'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62', 'azg_pick_actions', 'azg_env_playouts',
     'azg_eval_losses',
 ]
@@ -124,14 +124,9 @@ def lib():
         L.azg_eval_hashnet.argtypes = [vp, vp, i, i, i, i, vp, vp, vp]
     if hasattr(L, 'azg_forest_set_search_params'):          # (absent from older builds loaded through AZG_LIB for A/B runs)
         L.azg_forest_set_search_params.argtypes = [vp, i, dbl]
-    L.azg_nn_linear.argtypes = [vp, i, vp, i, i, vp, vp, i, vp, i, vp, i, i, i, i, i, i, vp]
-    L.azg_nn_linear_ws.argtypes = [vp, i, vp, i, i, vp, vp, i, vp, i, vp, i, i, i, i, i, vp]
-    L.azg_nn_v80_block.argtypes = [vp, vp, vp, i, i, i, vp]
-    L.azg_nn_v80_forward.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp]
-    L.azg_nn_v80_forward_split.argtypes = [vp, vp, vp, i, i, vp, vp, vp, vp]
+    L.azg_nn_v80_forward.argtypes = [vp, vp, vp, i, i, vp, vp, vp]
+    L.azg_nn_v80_forward_split.argtypes = [vp, vp, vp, i, i, vp, vp, vp]
     L.azg_nn_v80_forward_h2.argtypes = [vp, vp, vp, vp, i, i, vp, vp, vp]
-    L.azg_nn_dw_pool.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, i, vp]
-    L.azg_nn_board_to_x.argtypes = [vp, vp, i, i, vp]
     L.azg_nn_s78_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
     L.azg_nn_s78_forward_split.argtypes = [vp, vp, vp, i, i, i, i, vp, vp, vp]
     L.azg_nn_s78_forward_h2.argtypes = [vp, vp, vp, C.c_float, C.c_float, i, i, i, i, vp, vp, vp, vp]
@@ -144,9 +139,6 @@ def lib():
     L.azg_nn_conv5_forward_h2.argtypes = [vp, vp, vp, C.c_float, i, i, i, i, vp, vp, vp]
     L.azg_nn_mb1d_forward.argtypes = [i, vp, vp, vp, i, vp, vp, vp]
     L.azg_nn_mb1d_forward_h2.argtypes = [i, vp, vp, vp, vp, i, vp, vp, vp]
-    L.azg_nn_board_to_x_ld.argtypes = [vp, vp, i, i, i, i, vp]
-    L.azg_nn_dw_pool_l.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, i, i, vp]
-    L.azg_nn_heads_out.argtypes = [vp, i, vp, vp, i, vp, vp, vp, vp, i, i, i, vp]
     _lib = L
     return L
 

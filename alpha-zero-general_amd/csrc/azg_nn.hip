@@ -24,143 +24,10 @@
 
 using namespace azg;
 
-// ---- policy/value net building blocks (NeuralNet.predict, GenericNNetWrapper.py:94-120; V80: SplendorNNet.py:262-283) ----
-template <int NT, int KSPLIT, int NCH>
-static int launch_linear(const float* A, int lda, const float* Wp, const float* bias, const float* R, int ldr,
-                         const float* rowscale, int rpg, float* out, int ldc, int M, int K, int Kp, int N, int act,
-                         hipStream_t s) {
-    constexpr int NP = NT * 16;
-    const int tiles = (M + 15) / 16;
-    size_t lds;
-    int grid;
-    if (KSPLIT) {
-        lds = (size_t)4 * NT * 4 * 64 * sizeof(float);
-        grid = tiles;
-    } else {
-        lds = (size_t)Kp * NP * sizeof(float);
-        grid = (tiles + 3) / 4;
-        if (grid > 512) grid = 512;
-    }
-    if (lds > AZG_LDS_MAX) return fail("azg_nn_linear: weight tile exceeds LDS");
-    return launch_lds<k_linear<NT, KSPLIT, NCH>>(dim3(grid), dim3(256), lds, s, A, lda, Wp, bias, R, ldr, rowscale, rpg, out, ldc, M, K, Kp, N, act);
-}
-
-extern "C" int azg_nn_linear(const float* A, int lda, const float* Wp, int Kp, int NP, const float* bias, const float* R,
-                             int ldr, const float* rowscale, int rows_per_group, float* out, int ldc, int M, int K, int N,
-                             int act, int ksplit, void* stream) {
-    if (!A || !Wp || !out || M <= 0) return fail("azg_nn_linear: null/empty argument");
-    if (K % 4 || lda % 4 || Kp % 16 || Kp < K || NP % 16 || NP < N || (rowscale && rows_per_group <= 0))
-        return fail("azg_nn_linear: K, lda multiples of 4; Wp padded to [Kp % 16 == 0][NP % 16 == 0]");
-    hipStream_t s = (hipStream_t)stream;
-    const int nt = NP / 16;
-    const int chunks = Kp / 16;
-    const int per_wave = ksplit ? (chunks + 3) / 4 : chunks;
-    const int nch = per_wave <= 2 ? 2 : (per_wave <= 4 ? 4 : (per_wave <= 7 ? 7 : (per_wave <= 11 ? 11 : 0)));
-    if (!nch) return fail("azg_nn_linear: K too long for this variant (K <= 176, or <= 704 with ksplit)");
-#define ARGS A, lda, Wp, bias, R, ldr, rowscale, rows_per_group, out, ldc, M, K, Kp, N, act, s
-#define LIN_N(NTV, KS)                                                                     \
-    switch (nch) {                                                                         \
-        case 2: return launch_linear<NTV, KS, 2>(ARGS);                                    \
-        case 4: return launch_linear<NTV, KS, 4>(ARGS);                                    \
-        case 7: return launch_linear<NTV, KS, 7>(ARGS);                                    \
-        default: return launch_linear<NTV, KS, 11>(ARGS);                                  \
-    }
-#define LIN(NTV) do { if (ksplit) { LIN_N(NTV, 1) } else { LIN_N(NTV, 0) } } while (0)
-    switch (nt) {
-        case 1: LIN(1);
-        case 4: LIN(4);
-        case 6: LIN(6);
-        case 11: LIN(11);
-        case 12: LIN(12);
-        default: return fail("azg_nn_linear: NP/16 must be 1, 4, 6, 11 or 12");
-    }
-#undef LIN
-#undef LIN_N
-#undef ARGS
-}
-
-template <int NCH>
-static int launch_linear_ws(const float* A, int lda, const float* Wp, int NP, const float* biasp, const float* R, int ldr,
-                            const float* rowscale, int rpg, float* out, int ldc, int M, int K, int N, int act,
-                            hipStream_t s) {
-    const int tiles = (M + 15) / 16;
-    const int col_groups = ((N + 15) / 16 + 3) / 4;
-    // enough workgroups to fill the chip (~2048 waves), but several row tiles per wave so the weight fragment and the
-    // software prefetch are amortised
-    int tiles_per_wg = (tiles * col_groups + 2047) / 2048;
-    if (tiles_per_wg < 1) tiles_per_wg = 1;
-    const int gx = (tiles + tiles_per_wg - 1) / tiles_per_wg;
-    k_linear_ws<NCH><<<dim3(gx, col_groups), dim3(256), 0, s>>>(A, lda, Wp, NP, biasp, R, ldr, rowscale, rpg, out, ldc, M, K, N,
-                                                                act, tiles_per_wg);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int azg_nn_linear_ws(const float* A, int lda, const float* Wp, int Kp, int NP, const float* bias_padded,
-                                const float* R, int ldr, const float* rowscale, int rows_per_group, float* out, int ldc,
-                                int M, int K, int N, int act, void* stream) {
-    if (!A || !Wp || !out || M <= 0) return fail("azg_nn_linear_ws: null/empty argument");
-    if (K % 4 || lda % 4 || ldc % 4 || (R && ldr % 4) || Kp % 16 || Kp < K || NP % 16 || NP < N ||
-        (rowscale && rows_per_group <= 0))
-        return fail("azg_nn_linear_ws: K, lda, ldc, ldr multiples of 4; Wp padded to [Kp % 16 == 0][NP % 16 == 0]");
-    hipStream_t s = (hipStream_t)stream;
-#define WS(NCHV) return launch_linear_ws<NCHV>(A, lda, Wp, NP, bias_padded, R, ldr, rowscale, rows_per_group, out, ldc, M, K, N, act, s)
-    switch (Kp / 16) {
-        case 1: WS(1);
-        case 2: WS(2);
-        case 3: WS(3);
-        case 4: WS(4);
-        case 6: WS(6);
-        case 8: WS(8);
-        case 11: WS(11);
-        case 17: WS(17);
-        case 25: WS(25);
-        default: return fail("azg_nn_linear_ws: Kp/16 must be 1, 2, 3, 4, 6, 8, 11, 17 or 25");
-    }
-#undef WS
-}
-
-extern "C" int azg_nn_dw_pool_l(float* H, int ldh, const float* Wd, const float* sd, const float* bd, float* pooled, int B,
-                                int E, int L, int act, int pool_max, void* stream) {
-    if (!H || !Wd || !pooled || B <= 0) return fail("azg_nn_dw_pool: null/empty argument");
-    const long long total = (long long)B * E;
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (L == 7) k_dw_pool<7><<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(H, ldh, Wd, sd, bd, pooled, B, E, act, pool_max);
-    else if (L == 6) k_dw_pool<6><<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(H, ldh, Wd, sd, bd, pooled, B, E, act, pool_max);
-    else if (L == 2) k_dw_pool<2><<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(H, ldh, Wd, sd, bd, pooled, B, E, act, pool_max);
-    else if (L == 15) k_dw_pool<15><<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(H, ldh, Wd, sd, bd, pooled, B, E, act, pool_max);
-    else return fail("azg_nn_dw_pool: token count must be 2, 6, 7 or 15 (Minivilles, Azul, Splendor, The Little Prince)");
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int azg_nn_dw_pool(float* H, int ldh, const float* Wd, const float* sd, const float* bd, float* pooled, int B,
-                              int E, int act, int pool_max, void* stream) {
-    return azg_nn_dw_pool_l(H, ldh, Wd, sd, bd, pooled, B, E, 7, act, pool_max, stream);
-}
-
-template <int A_, int P_, int M_>
-static int launch_v80(const float* xin, float* xout, const V80BlockW& W, int B, const int8_t* boards, const V80NetW& N,
-                      const uint8_t* valid, float* pi, float* v, int P, hipStream_t s) {
-    return launch_lds<k_v80_block<A_, P_, M_>>(dim3((B + 15) / 16), dim3(768), V80_LDS, s, xin, xout, W, B, boards, N, valid, pi, v, P);
-}
-
-extern "C" int azg_nn_v80_block(const float* xin, float* xout, const float* const* w /* 11 device pointers */, int B,
-                                int act, int pool_max, void* stream) {
-    if (!xin || !xout || !w || B <= 0) return fail("azg_nn_v80_block: null/empty argument");
-    V80BlockW W{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10]};
-    V80NetW N{};
-    hipStream_t s = (hipStream_t)stream;
-    if (act == 1 && !pool_max) return launch_v80<1, 0, 0>(xin, xout, W, B, nullptr, N, nullptr, nullptr, nullptr, 0, s);
-    if (act == 1 && pool_max) return launch_v80<1, 1, 0>(xin, xout, W, B, nullptr, N, nullptr, nullptr, nullptr, 0, s);
-    if (act == 2 && !pool_max) return launch_v80<2, 0, 0>(xin, xout, W, B, nullptr, N, nullptr, nullptr, nullptr, 0, s);
-    if (act == 2 && pool_max) return launch_v80<2, 1, 0>(xin, xout, W, B, nullptr, N, nullptr, nullptr, nullptr, 0, s);
-    return fail("azg_nn_v80_block: act must be 1 (ReLU) or 2 (Hardswish)");
-}
-
+// ---- the V80 forward on f32 / bf16 x 3 operands, one launch (nn_kernels.hip.h; NeuralNet.predict, GenericNNetWrapper.py:94-120; V80: SplendorNNet.py:262-283) ----
 static int v80_forward(const int8_t* boards, const uint8_t* valid, const float* const* w /* 43 */, int B,
-                       int P, float* x_trunk, float* pi, float* v, void* stream, bool split) {
-    if (!boards || !valid || !w || !x_trunk || !pi || !v || B <= 0) return fail("azg_nn_v80_forward: null/empty argument");
+                       int P, float* pi, float* v, void* stream, bool split) {
+    if (!boards || !valid || !w || !pi || !v || B <= 0) return fail("azg_nn_v80_forward: null/empty argument");
     if (P < 2 || P > 4) return fail("azg_nn_v80_forward: 2 <= P <= 4");
     V80BlockW Wt{w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11], w[12]};
     V80BlockW Wp{w[13], w[14], w[15], w[16], w[17], w[18], w[19], w[20], w[21], w[22], w[23]};
@@ -171,24 +38,18 @@ static int v80_forward(const int8_t* boards, const uint8_t* valid, const float* 
     hipStream_t s = (hipStream_t)stream;
     // V80 geometry (SplendorNNet.py:262-283): trunk ReLU + mean-SE, both heads Hardswish + max-SE
     if (split) return launch_lds<k_v80_net_spx>(dim3((B + 15) / 16), dim3(768), V80_SPX_LDS, s, Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
-    if (getenv("AZG_NN_THREE_LAUNCHES")) {       // the per-block path (kept for A/B measurements)
-        if (launch_v80<1, 0, 1>(nullptr, x_trunk, Wt, B, boards, N0, nullptr, nullptr, nullptr, P, s)) return -1;
-        if (launch_v80<2, 1, 2>(x_trunk, nullptr, Wp, B, nullptr, Np, valid, pi, nullptr, P, s)) return -1;
-        if (launch_v80<2, 1, 3>(x_trunk, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v, P, s)) return -1;
-        return 0;
-    }
     return launch_lds<k_v80_net>(dim3((B + 15) / 16), dim3(768), V80_NET_LDS, s, Wt, Wp, Wv, N0, Np, Nv, boards, valid, B, P, pi, v);
 }
 
 
 extern "C" int azg_nn_v80_forward(const int8_t* boards, const uint8_t* valid, const float* const* w /* 43 */, int B,
-                                  int P, float* x_trunk, float* pi, float* v, void* stream) {
-    return v80_forward(boards, valid, w, B, P, x_trunk, pi, v, stream, false);
+                                  int P, float* pi, float* v, void* stream) {
+    return v80_forward(boards, valid, w, B, P, pi, v, stream, false);
 }
 
 extern "C" int azg_nn_v80_forward_split(const int8_t* boards, const uint8_t* valid, const float* const* w /* 43 */, int B,
-                                        int P, float* x_trunk, float* pi, float* v, void* stream) {
-    return v80_forward(boards, valid, w, B, P, x_trunk, pi, v, stream, true);
+                                        int P, float* pi, float* v, void* stream) {
+    return v80_forward(boards, valid, w, B, P, pi, v, stream, true);
 }
 
 // The V80 forward on fp16 hi+lo split operands with token-major tiles (nn_v80_h2.hip.h): one launch, one workgroup per 16 samples
@@ -403,29 +264,6 @@ extern "C" int azg_nn_bot_forward(const int8_t* boards, const uint8_t* valid, co
         if (!w[i]) return fail("azg_nn_bot_forward: null weight pointer");
     BotNetW N{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9]};
     return n_mach == 1 ? bot_launch<1>(N, boards, valid, B, pi, v, (hipStream_t)stream) : bot_launch<2>(N, boards, valid, B, pi, v, (hipStream_t)stream);
-}
-
-extern "C" int azg_nn_board_to_x_ld(const int8_t* boards, float* x, int B, int C, int L, int ldx, void* stream) {
-    if (!boards || !x || B <= 0 || L <= 0 || ldx < C) return fail("azg_nn_board_to_x: null/empty argument");
-    const long long total = (long long)B * L * ldx;
-    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-    k_board_to_x<<<dim3(grid), dim3(256), 0, (hipStream_t)stream>>>(boards, x, B, C, L, ldx);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int azg_nn_board_to_x(const int8_t* boards, float* x, int B, int C, void* stream) {
-    return azg_nn_board_to_x_ld(boards, x, B, C, 7, C, stream);
-}
-
-extern "C" int azg_nn_heads_out(const float* logits, int ldl, const uint8_t* valid, const float* vhid, int ldv,
-                                const float* Wv2, const float* bv2, float* pi, float* v, int B, int A, int P,
-                                void* stream) {
-    if (!logits || !valid || !pi || !v || B <= 0) return fail("azg_nn_heads_out: null/empty argument");
-    if (A > 256 || P > 4) return fail("azg_nn_heads_out: A <= 256, P <= 4");
-    k_heads_out<<<dim3(B), dim3(64), 0, (hipStream_t)stream>>>(logits, ldl, valid, vhid, ldv, Wv2, bv2, pi, v, B, A, P);
-    HIPCHK(hipGetLastError());
-    return 0;
 }
 
 #include "azg_fused.hip.h"

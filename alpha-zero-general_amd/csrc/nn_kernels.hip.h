@@ -1,17 +1,16 @@
-// nn_kernels.hip.h -- fp32 policy/value net building blocks for gfx950 (the only MFMA work on the self-play path).
+// nn_kernels.hip.h -- the shared device helpers of the policy/value net kernels for gfx950, and the one-launch V80 forward on f32 /
+// bf16 x 3 operands.
 //
 // The reference evaluates the net with ONNX Runtime / torch on the CPU, one leaf at a time or 8 at a time
-// (GenericNNetWrapper.py:94-157).  Here one lock-step round evaluates T leaves at once; the V80 network
-// (splendor/SplendorNNet.py:262-283,397-440) is a chain of *skinny* GEMMs (M = 7*T rows, K,N in {56,168,392,81}) plus
-// per-(sample,channel) glue, so instead of library GEMM calls (which pick poor tiles for K = 56) there are three kernels (+ a layout kernel):
-//
-//   k_linear      out = act(A' @ W + bias) (+ R)      MFMA v_mfma_f32_16x16x4_f32 (exact f32, == an fmaf chain), weights
-//                                                      resident in LDS, A fragments straight from HBM as float4;
-//                                                      A' = A optionally scaled per (sample,k) -- this fuses the
-//                                                      SqueezeExcitation multiply into the project GEMM's operand
-//   k_dw_pool     depthwise Linear(7->7) over the token axis + folded BN + activation + SE squeeze (avg / max)
-//                 (the two SE fully-connected layers E -> Q -> E are two more k_linear launches, hardsigmoid epilogue)
-//   k_heads_out   masked softmax of the policy logits (exp(log_softmax), GenericNNetWrapper.py:107) and the value tail
+// (GenericNNetWrapper.py:94-157).  Here one lock-step round evaluates T leaves at once, every net in one launch: the kernels of the other
+// nn_*.hip.h headers include this one for
+//   nn_tid, the bf16 x 3 split helpers and the plane layout (split3*, store_split4 / load_split4), nn_wave_max / nn_wave_sum,
+//   act_apply / act_apply2 / hardsigmoid and the f32 MFMA fragment order (FRAG).
+// The V80 network (splendor/SplendorNNet.py:262-283,397-440) is a chain of *skinny* GEMMs (M = 7*T rows, K,N in {56,168,392,81}) plus
+// per-(sample,channel) glue; v80_block_body runs one InvertedResidual1d block of it on a 16-sample tile held in LDS, and
+//   k_v80_net      first layer + trunk block + both head blocks and tails, MFMA v_mfma_f32_16x16x4_f32 throughout (exact f32)
+//   k_v80_net_spx  the same with the tile the blocks read kept as three bf16 planes and the expand GEMMs on bf16 x 3 operands
+// are the full-range forms of the forward (include/azg.h, "Activation range"); the default f16 x 2 form is nn_v80_h2.hip.h.
 #pragma once
 // the non-template kernels of this header get internal linkage in a translation unit that only wants its device helpers (azg_async.hip)
 #ifndef AZG_NN_KERNEL
@@ -132,244 +131,12 @@ __device__ __forceinline__ f32x2 act_apply2(f32x2 x, int act) {
 }
 __device__ __forceinline__ float hardsigmoid(float x) { return fminf(fmaxf(x + 3.f, 0.f), 6.f) * (1.f / 6.f); }
 
-// out[M][N] = act(A'[M][K] @ W + bias[N]) (+ R[M][N]);  A'[r][k] = A[r][k] * rowscale[r / rpg][k] if rowscale.
-//
-// W is pre-padded by the host to Wp[Kp][NP] (Kp = K rounded up to 16, NP = 16*NT, zero padding) so that staging and
-// fragment reads need no bounds logic.  MFMA 16x16x4 f32: lane l supplies A[row = l&15][k'] and B[k'][col = l&15] for the
-// k' of its lane group g = l>>4.  The reduction order over K is free as long as A and B agree, so group g takes
-// k' = 16*s + 4*g + j (j = 0..3) of K-chunk s: every lane then reads ONE float4 of its A row per chunk straight from
-// global memory (16 rows x 64 contiguous bytes per wave instruction) and A never goes through LDS.
-//   KSPLIT == 0 (tall M): Wp resident in LDS, each wave walks its own 16-row tiles, no barrier in the tile loop.
-//   KSPLIT == 1 (M ~ T, long K: the flatten->Linear heads): one 16-row tile per workgroup, the 4 waves split the K
-//               chunks, B fragments come straight from L2, partial sums are reduced through LDS.
-template <int NT, int KSPLIT, int NCH>
-__global__ __launch_bounds__(256) void k_linear(const float* __restrict__ A, int lda, const float* __restrict__ Wp,
-                                                const float* __restrict__ bias, const float* __restrict__ R, int ldr,
-                                                const float* __restrict__ rowscale, int rpg, float* __restrict__ out,
-                                                int ldc, int M, int K, int Kp, int N, int act) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int NP = NT * 16;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int n_chunks = Kp >> 4;
-    const int n_tiles = (M + 15) / 16;
-    if (!KSPLIT) {
-        // async global->LDS DMA (global_load_lds_dwordx4): 1 KiB per wave instruction, destination = uniform base +
-        // lane*16, all requests in flight at once (Kp*NP*4 is a multiple of 1 KiB because Kp and NP are multiples of 16)
-        const int n_kb = (Kp * NP) >> 8;
-        for (int c = wave; c < n_kb; c += 4)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Wp + (size_t)c * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(smem + (size_t)c * 256), 16, 0, 0);
-        __syncthreads();
-    }
-    const int tile_step = KSPLIT ? gridDim.x : gridDim.x * 4;
-    for (int tile = KSPLIT ? blockIdx.x : blockIdx.x * 4 + wave; tile < n_tiles; tile += tile_step) {
-        const int row = tile * 16 + r16;
-        const bool row_ok = row < M;
-        const float* arow = A + (size_t)(row_ok ? row : 0) * lda;
-        const float* srow = rowscale ? rowscale + (size_t)((row_ok ? row : 0) / rpg) * K : nullptr;
-        f32x4 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; nt++) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // all A chunks of this tile are requested up front (NCH float4 per lane) so the HBM latency is paid once
-        float4 av[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            const int s = KSPLIT ? wave + 4 * c : c;
-            const int k0 = 16 * s + 4 * g;
-            av[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (row_ok && s < n_chunks && k0 < K) av[c] = *(const float4*)(arow + k0);
-        }
-        if (srow) {
-#pragma unroll
-            for (int c = 0; c < NCH; c++) {
-                const int s = KSPLIT ? wave + 4 * c : c;
-                const int k0 = 16 * s + 4 * g;
-                if (row_ok && s < n_chunks && k0 < K) {
-                    const float4 sc = *(const float4*)(srow + k0);
-                    av[c].x *= sc.x; av[c].y *= sc.y; av[c].z *= sc.z; av[c].w *= sc.w;
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            const int s = KSPLIT ? wave + 4 * c : c;
-            if (s < n_chunks) {
-                const int k0 = 16 * s + 4 * g;
-                const float* wb = (KSPLIT ? Wp : smem) + (size_t)k0 * NP + r16;
-                const float a4[4] = {av[c].x, av[c].y, av[c].z, av[c].w};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-#pragma unroll
-                    for (int nt = 0; nt < NT; nt++)
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], wb[j * NP + nt * 16], acc[nt], 0, 0, 0);
-                }
-            }
-        }
-        if (KSPLIT) {
-            // reduce the 4 waves' partial tiles through LDS: red[wave][nt][reg][lane]
-            __syncthreads();
-            float* red = smem;
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) red[((wave * NT + nt) * 4 + r) * 64 + lane] = acc[nt][r];
-            __syncthreads();
-            if (wave == 0) {
-#pragma unroll
-                for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        acc[nt][r] = ((red[((0 * NT + nt) * 4 + r) * 64 + lane] + red[((1 * NT + nt) * 4 + r) * 64 + lane]) +
-                                      red[((2 * NT + nt) * 4 + r) * 64 + lane]) + red[((3 * NT + nt) * 4 + r) * 64 + lane];
-            }
-        }
-        if (!KSPLIT || wave == 0) {
-            // epilogue: C/D layout col = lane & 15, row = (lane >> 4) * 4 + reg
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) {
-                const int col = nt * 16 + r16;
-                if (col < N) {
-                    const float b = bias ? bias[col] : 0.f;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int orow = tile * 16 + g * 4 + r;
-                        if (orow < M) {
-                            float v = act_apply(acc[nt][r] + b, act);
-                            if (R) v += R[(size_t)orow * ldr + col];
-                            out[(size_t)orow * ldc + col] = v;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
-// Weight-stationary variant (the one the net uses): out^T = W^T @ A'^T.  The WEIGHT tile is the MFMA "A" operand and
-// lives in registers for the whole kernel (NCH*4 VGPRs per lane for one 16-column tile), activations are the "B" operand:
-// lane (g = l>>4, r = l&15) reads ONE float4 of activation row `tile*16 + r` per 16-wide K chunk straight from HBM/L2.
-// No LDS, no barrier; the C/D layout (i = 4*g + reg -> output column, j = r -> row) leaves every lane with 4 CONSECUTIVE
-// output columns of its row, so bias / activation / residual / store are float4-wide.  A workgroup's 4 waves take 4
-// different column tiles of the same row tiles (activation re-reads hit L1); grid.y covers the remaining column tiles.
-// The next row tile's activations (and residual) are requested before the current tile's MFMAs (software prefetch).
-template <int NCH>
-__global__ __launch_bounds__(256) void k_linear_ws(const float* __restrict__ A, int lda, const float* __restrict__ Wp,
-                                                   int NP, const float* __restrict__ biasp, const float* __restrict__ R,
-                                                   int ldr, const float* __restrict__ rowscale, int rpg,
-                                                   float* __restrict__ out, int ldc, int M, int K, int N, int act,
-                                                   int tiles_per_wg) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, r16 = lane & 15;
-    const int nt = blockIdx.y * 4 + wave;
-    if (nt * 16 >= N) return;
-    float w[NCH][4];
-#pragma unroll
-    for (int c = 0; c < NCH; c++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) w[c][j] = Wp[(size_t)(16 * c + 4 * g + j) * NP + nt * 16 + r16];
-    const int col0 = nt * 16 + 4 * g;
-    const float4 b4 = biasp ? *(const float4*)(biasp + col0) : make_float4(0.f, 0.f, 0.f, 0.f);
-    const int n_tiles = (M + 15) / 16;
-    const int t_begin = blockIdx.x * tiles_per_wg;
-    const int t_end = min(n_tiles, t_begin + tiles_per_wg);
-    float4 a_nxt[NCH];
-    float4 r_nxt = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto fetch = [&](int tile) {
-        const int row = tile * 16 + r16;
-        const bool ok = row < M;
-        const float* arow = A + (size_t)(ok ? row : 0) * lda;
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            const int k0 = 16 * c + 4 * g;
-            a_nxt[c] = (ok && k0 < K) ? *(const float4*)(arow + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (rowscale) {
-            const float* srow = rowscale + (size_t)((ok ? row : 0) / rpg) * K;
-#pragma unroll
-            for (int c = 0; c < NCH; c++) {
-                const int k0 = 16 * c + 4 * g;
-                if (ok && k0 < K) {
-                    const float4 sc = *(const float4*)(srow + k0);
-                    a_nxt[c].x *= sc.x; a_nxt[c].y *= sc.y; a_nxt[c].z *= sc.z; a_nxt[c].w *= sc.w;
-                }
-            }
-        }
-        if (R) r_nxt = (ok && col0 + 3 < ((N + 3) & ~3)) ? *(const float4*)(R + (size_t)row * ldr + col0)
-                                                          : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    if (t_begin < t_end) fetch(t_begin);
-    for (int tile = t_begin; tile < t_end; tile++) {
-        float4 a_cur[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; c++) a_cur[c] = a_nxt[c];
-        const float4 r_cur = r_nxt;
-        if (tile + 1 < t_end) fetch(tile + 1);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < NCH; c++) {
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][0], a_cur[c].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][1], a_cur[c].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][2], a_cur[c].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[c][3], a_cur[c].w, acc, 0, 0, 0);
-        }
-        const int row = tile * 16 + r16;
-        if (row < M) {
-            float4 v;
-            v.x = act_apply(acc[0] + b4.x, act) + r_cur.x;
-            v.y = act_apply(acc[1] + b4.y, act) + r_cur.y;
-            v.z = act_apply(acc[2] + b4.z, act) + r_cur.z;
-            v.w = act_apply(acc[3] + b4.w, act) + r_cur.w;
-            float* o = out + (size_t)row * ldc + col0;
-            if (col0 + 3 < N) *(float4*)o = v;
-            else {
-                if (col0 + 0 < N) o[0] = v.x;
-                if (col0 + 1 < N) o[1] = v.y;
-                if (col0 + 2 < N) o[2] = v.z;
-            }
-        }
-    }
-}
-
-// H[b*L + m][c] <- act( sd[c] * sum_l Wd[m][l] * H[b*L + l][c] + bd[c] );  pooled[b][c] = mean_m / max_m of the result
-// (L = 7 tokens for Splendor, 6 for Azul)
-// (LinearNormActivation depthwise + SqueezeExcitation1d pooling, SplendorNNet.py:148-187).  One (sample, channel) per
-// thread, channel-fastest => coalesced; wide grid for memory-level parallelism (2 x 19 MB of traffic at T = 4096).
-template <int L>
-__global__ __launch_bounds__(256) void k_dw_pool(float* __restrict__ H, int ldh, const float* __restrict__ Wd,
-                                                 const float* __restrict__ sd, const float* __restrict__ bd,
-                                                 float* __restrict__ pooled, int B, int E, int act, int pool_max) {
-    __shared__ float w[L * L];
-    if (threadIdx.x < L * L) w[threadIdx.x] = Wd[threadIdx.x];
-    __syncthreads();
-    const long long total = (long long)B * E;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / E), c = (int)(i - (long long)b * E);
-        float* base = H + (size_t)b * L * ldh + c;
-        float in[L];
-#pragma unroll
-        for (int l = 0; l < L; l++) in[l] = base[(size_t)l * ldh];
-        const float s = sd[c], bb = bd[c];
-        float pool = pool_max ? -INFINITY : 0.f;
-#pragma unroll
-        for (int m = 0; m < L; m++) {
-            float a = 0.f;
-#pragma unroll
-            for (int l = 0; l < L; l++) a += w[m * L + l] * in[l];
-            a = act_apply(a * s + bb, act);
-            base[(size_t)m * ldh] = a;
-            pool = pool_max ? fmaxf(pool, a) : pool + a;
-        }
-        pooled[(size_t)b * E + c] = pool_max ? pool : pool / (float)L;
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Fused InvertedResidual1d block (SplendorNNet.py:189-202 with :148-187), one workgroup = 16 samples = 112 token rows:
 //   x[112][C=56] --expand GEMM+BN+act--> h[112][E=168] --depthwise Linear(7->7)+BN+act, SE squeeze--> pooled[16][E]
 //   --SE fc1+ReLU--> [16][Q=40] --SE fc2+Hardsigmoid--> sc[16][E];   out = (h * sc) @ Wp + BN + x      (project + residual)
-// The expanded activations (19 MB per block at T = 4096) never leave the CU: they live in LDS between the phases, so a
-// block costs one read of x and one write of out (2 x 6.4 MB) instead of ~115 MB of HBM traffic for the unfused chain.
+// The expanded activations (19 MB per block at T = 4096) never leave the CU: they live in LDS between the phases, and so do
+// the block's input and output tiles (a launch per layer would move ~115 MB of HBM traffic per block).
 // All four GEMMs use MFMA f32 16x16x4 with the WEIGHTS as the A operand held in registers (prefetched from L2 at kernel
 // start, overlapping the x load) and the activations as the B operand read as float4 from LDS; 12 waves per workgroup:
 //   expand   11 column tiles x 7 row tiles      wave w < 11 owns column tile w
@@ -381,9 +148,9 @@ __global__ __launch_bounds__(256) void k_dw_pool(float* __restrict__ H, int ldh,
 struct V80BlockW {
     const float *We, *be, *Wd, *sd, *bd, *W1, *b1, *W2, *b2, *Wp, *bp;     // be/b1/b2/bp zero-padded to the padded widths
 };
-// What the whole-net fusion hangs onto the three blocks (k_v80_block MODE 1..3):
+// What the whole-net fusion hangs onto the three blocks (v80_block_body MODE 1..3):
 //   MODE 1 (trunk):       boards int8 [B][56][7] -> f32 tile (layout change in LDS) -> first_layer Linear(56,56)+BN
-//                         (SplendorNNet.py:397-401) -> block -> xout in HBM
+//                         (SplendorNNet.py:397-401) -> block -> output tile in LDS
 //   MODE 2 (policy head): block -> Flatten -> Linear(392,81)+ReLU -> Linear(81,81) -> masked softmax -> pi in HBM
 //   MODE 3 (value head):  block -> Flatten -> Linear(392,P)+ReLU -> Linear(P,P) -> tanh -> v in HBM   (:414-440)
 // The block output tile stays in LDS (in place of x, row stride 60), so the flatten index of the head weights is
@@ -409,21 +176,22 @@ static __device__ long long g_v80_phase[4][16];
 
 // The block (+ optional first layer in front, + optional head tail behind) on one 16-sample tile.  X = the tile's [112][60]
 // f32 buffer in LDS, H = the rest of the workgroup's LDS ([112][172] + 2 x [16][172] + [16][52] + 64 floats).
-//   INLDS:  the input tile is already in X (whole-net kernel) instead of xin in HBM
-//   OUTLDS: the block output replaces X in place (always the case for the head MODEs); SAVE: and is copied to xsave
+//   INLDS:  the input tile is already in X (the head MODEs; MODE 1 builds it from the boards)
+//   OUTLDS: the block output replaces X in place (MODE 1 sets it, the head MODEs always do: nothing but boards, valid, pi and v
+//           crosses HBM); SAVE: and is copied to xsave
 //   SPX:    the input tile lives in LDS as three bf16 planes [112][64] (hi + mid + lo, the layout of nn_conv5x5.hip.h) instead of
 //           the f32 [112][60] tile, written split once by the producing epilogue, and the expand GEMM runs on bf16 x 3 operands (six
 //           v_mfma_f32_16x16x32_bf16 per product; W.We = [11 tiles][2 K chunks of 32][3 planes][64 lanes][8] bf16).  The trunk block
 //           rewrites the planes in place; the head blocks leave them alone (the value head reuses the trunk output) and put their
 //           f32 output O [112][60] over the dead pooled / SE-hidden buffers for the head tail.
 template <int ACT, int POOLMAX, int MODE, bool INLDS, bool OUTLDS, bool SAVE, bool SPX = false>
-__device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave, const float* __restrict__ xin,
-                                               float* __restrict__ xout, const V80BlockW& W, int B,
+__device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave, const V80BlockW& W, int B,
                                                const int8_t* __restrict__ boards, const V80NetW& N,
                                                const uint8_t* __restrict__ valid, float* __restrict__ pi_out,
                                                float* __restrict__ v_out, int P) {
     constexpr int C = 56, E = 168, NS = 16, ROWS = NS * 7, XS = 60, HS = 172, QS = 52, FK = 7 * XS /* 420 */, A = 81;
-    static_assert(!SPX || ((MODE == 1 || INLDS) && !SAVE), "SPX: whole-net kernel only");
+    static_assert(MODE == 1 ? !INLDS && OUTLDS : (MODE == 2 || MODE == 3) && INLDS, "the tile stays in LDS from the boards to pi / v");
+    static_assert(!SPX || !SAVE, "SPX: one copy of the trunk output serves both heads");
     // (SPX: SC first, so that pooled + SE hidden + depthwise weights + 12 KB behind them form the 26.9 KB of the head blocks' output tile)
     float* SC = SPX ? H + ROWS * HS : H + ROWS * HS + NS * HS;          // scales [NS][HS]
     float* PL = SPX ? SC + NS * HS : H + ROWS * HS;                     // pooled [NS][HS]
@@ -435,7 +203,6 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, r16 = lane & 15;
     const int b0 = blockIdx.x * NS;
-    const int nrows = min(ROWS, (B - b0) * 7);
     const int nt_p = wave & 3;
     AZG_PH(0);
 
@@ -512,28 +279,11 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
     }
 
     AZG_PH(1);
-    // ---- x tile requested first (HBM), then the weight fragments (L2) in the order the phases need them: the vmcnt
-    //      counter retires in order, so P0 / P1 only wait for what they use while the rest keeps streaming in ----
-    float4 xv[3];
-    if (MODE != 1 && !INLDS) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int i = tid + 768 * k, row = i / (XS / 4), c4 = i - row * (XS / 4);
-            xv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (i < ROWS * (XS / 4) && row < nrows && c4 < C / 4) xv[k] = *(const float4*)(xin + ((size_t)b0 * 7 + row) * C + 4 * c4);
-        }
-    }
+    // ---- the weight fragments (L2) are requested in the order the phases need them: the vmcnt counter retires in order,
+    //      so P1 only waits for what it uses while the rest keeps streaming in ----
     if (MODE != 1) load_we();
     const float4 be4 = *(const float4*)(W.be + nt_e * 16 + 4 * g);
     const float wd_stage = tid < 49 ? W.Wd[tid] : 0.f;       // requested now, parked in LDS after the expand phase (used by P2)
-    if (MODE != 1 && !INLDS) {
-        // ---- P0: x tile -> LDS (contiguous rows, float4); pad columns 56..59 zeroed ----
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int i = tid + 768 * k, row = i / (XS / 4), c4 = i - row * (XS / 4);
-            if (i < ROWS * (XS / 4)) *(float4*)(X + row * XS + 4 * c4) = xv[k];
-        }
-    }
     if (MODE != 1) load_w2_wp();
     const float4 b14 = *(const float4*)(W.b1 + nt_1 * 16 + 4 * g);
     const float4 b24 = *(const float4*)(W.b2 + nt_e * 16 + 4 * g);
@@ -682,7 +432,7 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
         }
     }
 
-    // ---- P5: project (SE-scaled operand) + BN + residual -> HBM (MODE 0/1) or in place of x in LDS (MODE 2/3) ----
+    // ---- P5: project (SE-scaled operand) + BN + residual -> in place of x in LDS ----
 #pragma unroll 1
     for (int rt = wave >> 2; rt < 7; rt += 3) {
         const int row = rt * 16 + r16;
@@ -710,7 +460,7 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
             const float4 o4 = make_float4(acc[0] + bp4.x + xr.x, acc[1] + bp4.y + xr.y, acc[2] + bp4.z + xr.z, acc[3] + bp4.w + xr.w);
             if (MODE == 1) store_split4(XPL, PB, row, col0, o4);     // trunk: in place, a lane rewrites the elements it read
             else if (col0 < XS) *(float4*)(OT + row * XS + col0) = o4;
-        } else if (MODE >= 2 || OUTLDS) {
+        } else {
             if (col0 < XS) {          // each element is read (residual) and overwritten by the same lane
                 float* xp = X + row * XS + col0;
                 const float4 xr = *(const float4*)xp;
@@ -719,12 +469,6 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
                 *(float4*)xp = o4;
                 if (SAVE) *(float4*)(xsave + row * XS + col0) = o4;
             }
-        } else if (row < nrows && col0 < C) {
-            const float4 xr = *(const float4*)(X + row * XS + col0);
-            float4 v;
-            v.x = acc[0] + bp4.x + xr.x; v.y = acc[1] + bp4.y + xr.y;
-            v.z = acc[2] + bp4.z + xr.z; v.w = acc[3] + bp4.w + xr.w;
-            *(float4*)(xout + ((size_t)b0 * 7 + row) * C + col0) = v;
         }
     }
 
@@ -833,21 +577,12 @@ __device__ __forceinline__ void v80_block_body(float* X, float* H, float* xsave,
     }
 }
 
-// dynamic LDS of the three kernels below (bytes): k_v80_block = X [112][60] + H of v80_block_body; k_v80_net = + a second [112][60] tile;
+// dynamic LDS of the two kernels below (bytes).  V80_LDS = X [112][60] + H of v80_block_body; k_v80_net = + a second [112][60] tile;
 // k_v80_net_spx = three bf16 planes [112][64] instead of X, + 12 KB behind H (the head blocks' output tile)
 constexpr size_t V80_LDS = (size_t)(112 * 60 + 112 * 172 + 2 * 16 * 172 + 16 * 52 + 64) * sizeof(float);
 constexpr size_t V80_NET_LDS = V80_LDS + (size_t)112 * 60 * sizeof(float);
 constexpr size_t V80_SPX_LDS = (size_t)3 * 112 * 128 + (V80_LDS - (size_t)112 * 60 * sizeof(float)) + 12288;
 static_assert(V80_LDS <= 160 * 1024 && V80_NET_LDS <= 160 * 1024 && V80_SPX_LDS <= 160 * 1024, "k_v80_*: LDS");
-template <int ACT, int POOLMAX, int MODE>
-AZG_NN_KERNEL __global__ __launch_bounds__(768) void k_v80_block(const float* __restrict__ xin, float* __restrict__ xout, V80BlockW W,
-                                                   int B, const int8_t* __restrict__ boards, V80NetW N,
-                                                   const uint8_t* __restrict__ valid, float* __restrict__ pi_out,
-                                                   float* __restrict__ v_out, int P) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    v80_block_body<ACT, POOLMAX, MODE, false, false, false>(smem, smem + 112 * 60, nullptr, xin, xout, W, B, boards, N, valid,
-                                                           pi_out, v_out, P);
-}
 
 // The whole V80 forward of one 16-sample tile in ONE workgroup pass: first layer + trunk block (its output stays in LDS and
 // is copied to a second tile buffer), policy head block + tail on the first copy, value head block + tail on the second.
@@ -859,11 +594,11 @@ AZG_NN_KERNEL __global__ __launch_bounds__(768) void k_v80_net(V80BlockW Wt, V80
     float* X = smem;
     float* XT = X + 112 * 60;
     float* H = XT + 112 * 60;
-    v80_block_body<1, 0, 1, false, true, true>(X, H, XT, nullptr, nullptr, Wt, B, boards, N0, nullptr, nullptr, nullptr, P);
+    v80_block_body<1, 0, 1, false, true, true>(X, H, XT, Wt, B, boards, N0, nullptr, nullptr, nullptr, P);
     __syncthreads();
-    v80_block_body<2, 1, 2, true, false, false>(X, H, nullptr, nullptr, nullptr, Wp, B, nullptr, Np, valid, pi_out, nullptr, P);
+    v80_block_body<2, 1, 2, true, false, false>(X, H, nullptr, Wp, B, nullptr, Np, valid, pi_out, nullptr, P);
     __syncthreads();
-    v80_block_body<2, 1, 3, true, false, false>(XT, H, nullptr, nullptr, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v_out, P);
+    v80_block_body<2, 1, 3, true, false, false>(XT, H, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v_out, P);
 }
 
 // The same forward with the tile the three blocks read kept as bf16 planes and the expand GEMMs on bf16 x 3 operands (SPX above):
@@ -874,52 +609,11 @@ AZG_NN_KERNEL __global__ __launch_bounds__(768) void k_v80_net_spx(V80BlockW Wt,
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* X = smem;                                  // three bf16 planes [112][64]
     float* H = X + 3 * 112 * 128 / 4;
-    v80_block_body<1, 0, 1, false, true, false, true>(X, H, nullptr, nullptr, nullptr, Wt, B, boards, N0, nullptr, nullptr, nullptr, P);
+    v80_block_body<1, 0, 1, false, true, false, true>(X, H, nullptr, Wt, B, boards, N0, nullptr, nullptr, nullptr, P);
     __syncthreads();
-    v80_block_body<2, 1, 2, true, false, false, true>(X, H, nullptr, nullptr, nullptr, Wp, B, nullptr, Np, valid, pi_out, nullptr, P);
+    v80_block_body<2, 1, 2, true, false, false, true>(X, H, nullptr, Wp, B, nullptr, Np, valid, pi_out, nullptr, P);
     __syncthreads();
-    v80_block_body<2, 1, 3, true, false, false, true>(X, H, nullptr, nullptr, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v_out, P);
-}
-
-// boards int8 [B][C][L] (reference layout) -> x f32 [B][L][ldx] (channels-last; columns C..ldx-1 zeroed)
-AZG_NN_KERNEL __global__ __launch_bounds__(256) void k_board_to_x(const int8_t* __restrict__ boards, float* __restrict__ x, int B, int C,
-                                                    int L, int ldx) {
-    const long long total = (long long)B * L * ldx;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(i / (L * ldx)), rem = (int)(i - (long long)b * L * ldx), l = rem / ldx, c = rem - l * ldx;
-        x[i] = c < C ? (float)boards[(size_t)b * L * C + c * L + l] : 0.f;
-    }
-}
-
-// pi[b] = softmax(where(valid, logits, -1e8)) ; v[b] = tanh(relu(vhid[b]) @ Wv2 + bv2)      one wave per sample
-AZG_NN_KERNEL __global__ __launch_bounds__(64) void k_heads_out(const float* __restrict__ logits, int ldl,
-                                                  const uint8_t* __restrict__ valid, const float* __restrict__ vhid,
-                                                  int ldv, const float* __restrict__ Wv2, const float* __restrict__ bv2,
-                                                  float* __restrict__ pi, float* __restrict__ v, int B, int A, int P) {
-    const int b = blockIdx.x, l = threadIdx.x;
-    if (b >= B) return;
-    float x[4];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int a = l + 64 * k;
-        x[k] = -INFINITY;
-        if (a < A) { x[k] = valid[(size_t)b * A + a] ? logits[(size_t)b * ldl + a] : -1e8f; mx = fmaxf(mx, x[k]); }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { x[k] = (l + 64 * k < A) ? expf(x[k] - mx) : 0.f; s += x[k]; }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-#pragma unroll
-    for (int k = 0; k < 4; k++) if (l + 64 * k < A) pi[(size_t)b * A + l + 64 * k] = x[k] / s;
-    if (l < P) {
-        float a = bv2[l];
-        for (int j = 0; j < P; j++) { float hj = vhid[(size_t)b * ldv + j]; a += (hj > 0.f ? hj : 0.f) * Wv2[j * P + l]; }
-        v[(size_t)b * P + l] = tanhf(a);
-    }
+    v80_block_body<2, 1, 3, true, false, false, true>(X, H, nullptr, Wv, B, nullptr, Nv, nullptr, nullptr, v_out, P);
 }
 
 }  // namespace azg

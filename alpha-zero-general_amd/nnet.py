@@ -66,6 +66,33 @@ def _pad(t, shape):
     return out
 
 
+def _frag(Wp, half_last=False):
+    """zero-padded [Kp][NP] f32 -> MFMA fragment order [NP/16][Kp/16][64 lanes][4]:
+    frag[nt][c][lane][j] = Wp[16c + 4*(lane>>4) + j][16nt + (lane&15)]  (FRAG in csrc/nn_kernels.hip.h).
+    half_last: the last chunk holds only 8 rows of K; lane group g gets rows 16c + 2g + {0, 1} in j = 0, 1"""
+    Kp, NP = Wp.shape
+    assert Kp % 16 == 0 and NP % 16 == 0
+    if half_last:
+        last = Wp[Kp - 16:].clone()
+        assert float(last[8:].abs().max()) == 0.0
+        Wp = Wp.clone()
+        Wp[Kp - 16:] = 0
+        for g in range(4):
+            Wp[Kp - 16 + 4 * g: Kp - 16 + 4 * g + 2] = last[2 * g: 2 * g + 2]
+    return Wp.view(Kp // 16, 4, 4, NP // 16, 16).permute(3, 0, 1, 4, 2).contiguous().view(-1)
+
+
+def _r16(n):
+    return (n + 15) // 16 * 16
+
+
+def _flat_rows(Wf, L, stride):
+    """a flatten -> Linear weight [L*c][N] (row k = l*c + ch) re-indexed to the kernels' token tile of row stride `stride`:
+    [L*stride][N], row k = l*stride + ch (the pad rows zero)"""
+    c = Wf.shape[0] // L
+    return _pad(Wf.view(L, c, -1), (L, stride, Wf.shape[1])).view(L * stride, -1)
+
+
 class _TorchNet:
     """NeuralNet-style entry points of the plain-torch nets: a subclass has __init__(state_dict, ..., device=...), device and
     forward(boards, valids bool) -> (pi, v)."""
@@ -253,14 +280,15 @@ class SplendorV80(_TorchNet):
         return pi.contiguous(), v.contiguous()
 
 
-class SplendorV80Hip(SplendorV80, _EngineNet):
-    """Same network, same weights, evaluated by the engine's own gfx950 kernels (azg_nn_* in include/azg.h) instead of
-    ~70 torch ops: 9 skinny fp32 MFMA GEMMs (k_linear, with bias / activation / residual / SE-scale fused), 3
-    depthwise+BN+act+pool kernels, 3 SE kernels, one layout kernel and one softmax/value kernel per leaf batch.  Its own
-    activation buffers and forward; predict takes bool valids (SplendorV80's)."""
+class SplendorV80Hip(_EngineNet, SplendorV80):
+    """Same network, same weights, evaluated by one launch of the engine's own gfx950 kernels instead of ~70 torch ops per leaf batch:
+    first layer, the three InvertedResidual1d blocks and both head tails on a 16-sample tile that never leaves LDS (azg_nn_v80_forward*
+    in include/azg.h).  The weights are packed once, as three 43-slot pointer tables (f32, bf16 x 3 and f16 x 2 operands); forward and predict are
+    _EngineNet's (bool or uint8 valids), the torch model underneath is SplendorV80's."""
+    S = 56 * 7
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', max_batch=4096, split=True, h2=None):
-        """h2 (default for the 2-player geometry): the one-launch forward on fp16 hi+lo split operands with token-major tiles
+        """h2 (default for the 2-player geometry): the forward on fp16 hi+lo split operands with token-major tiles
         (azg_nn_v80_forward_h2, csrc/nn_v80_h2.hip.h; same 1e-5 contract).  Otherwise split: the tile the blocks read is kept as
         three bf16 planes and the expand GEMMs run on bf16 x 3 operands (azg_nn_v80_forward_split); False = f32 MFMAs throughout"""
         super().__init__(state_dict, num_players=num_players, device=device, dtype=torch.float32)
@@ -269,93 +297,43 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
         self.split = bool(split)
         self.h2 = (self.nb_vect == 56) if h2 is None else bool(h2)
         self.C = self.nb_vect
-        self.E = 3 * self.C
-        self.Q = self.trunk.W1.shape[1]
-        self.weight_stationary = True
-        self.fused_blocks = True
-        self.fused_net = True          # whole forward in one launch (azg_nn_v80_forward)
-        self._bias_pad = {}
-        self._prepare()
+        self.fused_net = True          # the one-launch forward is the only form there is (forest.py's matcher reads this)
+        self._net_ptrs()
+        self._h2_ptrs()
         self._alloc(max_batch)
 
-    def _alloc(self, B):
-        d, f = self.device, torch.float32
-        self.maxB = B
-        self.x0 = torch.empty((B * 7, self.C), dtype=f, device=d)
-        self.x1 = torch.empty((B * 7, self.C), dtype=f, device=d)
-        self.x2 = torch.empty((B * 7, self.C), dtype=f, device=d)
-        self.xh = torch.empty((B * 7, self.C), dtype=f, device=d)
-        self.h = torch.empty((B * 7, self.E), dtype=f, device=d)
-        self.pooled = torch.empty((B, self.E), dtype=f, device=d)
-        self.sc = torch.empty((B, self.E), dtype=f, device=d)
-        self.se_h = torch.zeros((B, 48), dtype=f, device=d)        # Q = 40 used, zero-padded to a multiple of 16 for K
-        self.hid_pi = torch.zeros((B, 96), dtype=f, device=d)      # 81 used, zero-padded to a multiple of 4 for K
-        self.logits = torch.empty((B, 96), dtype=f, device=d)
-        self.hid_v = torch.zeros((B, 16), dtype=f, device=d)
-        self.pi = torch.empty((B, self.A), dtype=f, device=d)
-        self.v = torch.empty((B, self.P), dtype=f, device=d)
-
-    @staticmethod
-    def _pad_w(W):
-        """[K][N] -> zero-padded [Kp][NP], Kp multiple of 16, NP/16 in {1,4,6,11} (k_linear's LDS / fragment layout)"""
-        K, N = W.shape
-        Kp = (K + 15) // 16 * 16
-        nt = (N + 15) // 16
-        out = torch.zeros((Kp, nt * 16), dtype=torch.float32, device=W.device)
-        out[:K, :N] = W
-        return out.contiguous()
-
-    def _prepare(self):
-        self.pW0 = self._pad_w(self.W0)
-        for blk in (self.trunk, self.head_pi, self.head_v):
-            blk.pWe, blk.pWp = self._pad_w(blk.We), self._pad_w(blk.Wp)
-            blk.pW1, blk.pW2 = self._pad_w(blk.W1), self._pad_w(blk.W2)
-        self.pWpi1, self.pWpi2 = self._pad_w(self.Wpi1), self._pad_w(self.Wpi2)
-        self.pWv1 = self._pad_w(self.Wv1)
-        for blk in (self.trunk, self.head_pi, self.head_v):
-            self._block_ptrs(blk)
-        self._net_ptrs()
-
     def _net_ptrs(self):
-        """device pointer table of azg_nn_v80_forward (include/azg.h): first layer, 3 blocks, head Linears re-indexed to the
-        in-LDS flatten k = l*60 + c"""
-        assert (self.trunk.use_hs, self.trunk.setype) == (False, 'avg')
-        assert (self.head_pi.use_hs, self.head_pi.setype) == (True, 'max') and (self.head_v.use_hs, self.head_v.setype) == (True, 'max')
+        """device pointer tables of azg_nn_v80_forward / _split (include/azg.h): first layer, 3 blocks, head Linears re-indexed to the
+        in-LDS flatten k = l*60 + c; _split differs in the three expand matrices only"""
+        blocks = (self.trunk, self.head_pi, self.head_v)
+        assert [(b.use_hs, b.setype) for b in blocks] == [(False, 'avg'), (True, 'max'), (True, 'max')]
         assert self.C == 56 and self.A == 81
-        d, f, pad = self.device, torch.float32, _pad
-
-        def flat60(Wf, ncols):        # [7*56][N] (k = l*56 + c) -> [432][ncols] (k = l*60 + c)
-            N = Wf.shape[1]
-            out = torch.zeros((432, ncols), dtype=f, device=d)
-            out[:420].view(7, 60, ncols)[:, :56, :N] = Wf.view(7, 56, N)
-            return out.contiguous()
-        head = [self._frag(flat60(self.Wpi1, 96)), pad(self.bpi1, (96,)), self._frag(pad(self.Wpi2, (96, 96))),
-                pad(self.bpi2, (96,)), self._frag(flat60(self.Wv1, 16)), pad(self.bv1, (16,)), self.Wv2.contiguous(),
-                self.bv2.contiguous()]
-        first = [self._frag(pad(self.W0, (64, 64)), True), pad(self.b0, (64,))]
-        self._net_keep = first + self.trunk._keep + self.head_pi._keep + self.head_v._keep + head
-        assert len(self._net_keep) == 43
-        self.net_ptrs = (C.c_void_p * 43)(*[t.data_ptr() for t in self._net_keep])
-        keep = list(self._net_keep)
-        for bi, blk in enumerate((self.trunk, self.head_pi, self.head_v)):
-            keep[2 + 11 * bi] = _split_frag(blk.pWe, 'bf16x3')   # [64][176] (K 56 -> 64 zero padded)
+        pad = _pad
+        keep = [_frag(pad(self.W0, (64, 64)), True), pad(self.b0, (64,))]
+        for blk in blocks:
+            keep += [_frag(pad(blk.We, (64, 176)), True), pad(blk.be, (176,)), blk.Wd.contiguous(), blk.sd.contiguous(), blk.bd.contiguous(),
+                     _frag(pad(blk.W1, (176, 48)), True), pad(blk.b1, (48,)), _frag(pad(blk.W2, (48, 176))), pad(blk.b2, (176,)),
+                     _frag(pad(blk.Wp, (176, 64)), True), pad(blk.bp, (64,))]
+        keep += [_frag(pad(_flat_rows(self.Wpi1, 7, 60), (432, 96))), pad(self.bpi1, (96,)), _frag(pad(self.Wpi2, (96, 96))),
+                 pad(self.bpi2, (96,)), _frag(pad(_flat_rows(self.Wv1, 7, 60), (432, 16))), pad(self.bv1, (16,)), self.Wv2.contiguous(),
+                 self.bv2.contiguous()]
+        assert len(keep) == 43
+        self._net_keep = keep
+        self.net_ptrs = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
+        keep = list(keep)
+        for bi, blk in enumerate(blocks):
+            keep[2 + 11 * bi] = _split_frag(pad(blk.We, (64, 176)), 'bf16x3')     # K 56 -> 64 zero padded
         self._net_keep_split = keep
         self.net_ptrs_split = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
-        self._h2_ptrs()
 
     def _h2_ptrs(self):
         """pointer table + descale factors of azg_nn_v80_forward_h2 (include/azg.h): every matrix zero padded to K % 32 == 0,
         N % 16 == 0, scaled by 2^k (max |w| * 2^k in (2^11, 2^12]) and split into f16 hi / lo fragments"""
-        d, f, pad = self.device, torch.float32, _pad
+        f, pad = torch.float32, _pad
 
         def frag(W, K, N):
             k = _pow2_scale(W.abs().max())
             return _split_frag(pad(W, (K, N)), 'h2', k), _descale(k)
-
-        def flat64(Wf, N):            # [7*56][N] (k = l*56 + c) -> [448][N] (k = l*64 + c)
-            out = torch.zeros((448, Wf.shape[1]), dtype=f, device=d)
-            out.view(7, 64, Wf.shape[1])[:, :56, :] = Wf.view(7, 56, Wf.shape[1])
-            return out
         keep, desc = [], []
         t, s = frag(self.W0, 64, 64)
         keep += [t, pad(self.b0, (64,))]
@@ -368,9 +346,9 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
             keep += [we, pad(blk.be, (176,)), (blk.Wd / 6.0 if blk.use_hs else blk.Wd).contiguous().to(f), pad(blk.sd, (176,)), pad(blk.bd, (176,)), w1, pad(blk.b1, (48,)),
                      w2, pad(blk.b2, (176,)), wp, pad(blk.bp, (64,))]
             desc += [se, s1, s2, sp]
-        wpi1, spi1 = frag(flat64(self.Wpi1, 96), 448, 96)
+        wpi1, spi1 = frag(_flat_rows(self.Wpi1, 7, 64), 448, 96)            # row k = l*64 + c
         wpi2, spi2 = frag(self.Wpi2, 96, 96)
-        wv1, sv1 = frag(flat64(self.Wv1, 16), 448, 16)
+        wv1, sv1 = frag(_flat_rows(self.Wv1, 7, 64), 448, 16)
         keep += [wpi1, pad(self.bpi1, (96,)), wpi2, pad(self.bpi2, (96,)), wv1, pad(self.bv1, (16,)), self.Wv2.contiguous(), self.bv2.contiguous()]
         desc += [spi1, spi2, sv1]
         assert len(keep) == 43 and len(desc) == 16
@@ -378,99 +356,13 @@ class SplendorV80Hip(SplendorV80, _EngineNet):
         self.net_ptrs_h2 = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
         self.descale_h2 = (C.c_float * 16)(*desc)
 
-    def _linear(self, A, lda, Wp, bias, out, ldc, M, K, N, act=0, R=None, ldr=0, rowscale=None, rpg=0, ksplit=0):
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if self.weight_stationary:
-            bp = None
-            if bias is not None:
-                key = bias.data_ptr()
-                bp = self._bias_pad.get(key)
-                if bp is None:
-                    bp = torch.zeros(Wp.shape[1], dtype=torch.float32, device=bias.device)
-                    bp[:bias.numel()] = bias
-                    self._bias_pad[key] = bp
-            self._lib.check(self._lib.lib().azg_nn_linear_ws(p(A), lda, p(Wp), Wp.shape[0], Wp.shape[1], p(bp), p(R), ldr,
-                                                             p(rowscale), rpg, p(out), ldc, M, K, N, act, self._stream()))
-            return
-        self._lib.check(self._lib.lib().azg_nn_linear(p(A), lda, p(Wp), Wp.shape[0], Wp.shape[1], p(bias), p(R), ldr,
-                                                      p(rowscale), rpg, p(out), ldc, M, K, N, act, ksplit,
-                                                      self._stream()))
-
-    @staticmethod
-    def _frag(Wp, half_last=False):
-        """zero-padded [Kp][NP] -> MFMA fragment order [NP/16][Kp/16][64 lanes][4]:
-        frag[nt][c][lane][j] = Wp[16c + 4*(lane>>4) + j][16nt + (lane&15)]  (FRAG in csrc/nn_kernels.hip.h).
-        half_last: the last chunk holds only 8 rows of K; lane group g gets rows 16c + 2g + {0, 1} in j = 0, 1"""
-        Kp, NP = Wp.shape
-        assert Kp % 16 == 0 and NP % 16 == 0
-        if half_last:
-            last = Wp[Kp - 16:].clone()
-            assert float(last[8:].abs().max()) == 0.0
-            Wp = Wp.clone()
-            Wp[Kp - 16:] = 0
-            for g in range(4):
-                Wp[Kp - 16 + 4 * g: Kp - 16 + 4 * g + 2] = last[2 * g: 2 * g + 2]
-        return Wp.view(Kp // 16, 4, 4, NP // 16, 16).permute(3, 0, 1, 4, 2).contiguous().view(-1)
-
-    def _block_ptrs(self, blk):
-        def pad1(v, n):
-            out = torch.zeros(n, dtype=torch.float32, device=v.device)
-            out[:v.numel()] = v
-            return out
-        blk._keep = [self._frag(blk.pWe, True), pad1(blk.be, 176), blk.Wd.contiguous(), blk.sd.contiguous(), blk.bd.contiguous(),
-                     self._frag(blk.pW1, True), pad1(blk.b1, 48), self._frag(blk.pW2), pad1(blk.b2, 176), self._frag(blk.pWp, True),
-                     pad1(blk.bp, 64)]
-        assert tuple(blk.pWe.shape) == (64, 176) and tuple(blk.pW1.shape) == (176, 48)
-        assert tuple(blk.pW2.shape) == (48, 176) and tuple(blk.pWp.shape) == (176, 64)
-        blk.ptrs = (C.c_void_p * 11)(*[t.data_ptr() for t in blk._keep])
-
-    def _block(self, blk, xin, xout, B):
+    def _launch(self, boards, valids, B, stream):
         L = self._lib.lib()
-        if self.fused_blocks:
-            self._lib.check(L.azg_nn_v80_block(C.c_void_p(xin.data_ptr()), C.c_void_p(xout.data_ptr()), blk.ptrs, B,
-                                               2 if blk.use_hs else 1, 0 if blk.setype == 'avg' else 1, self._stream()))
+        if self.h2:
+            self._lib.check(L.azg_nn_v80_forward_h2(boards, valids, self.net_ptrs_h2, self.descale_h2, B, self.P, _ptr(self.pi), _ptr(self.v), stream))
             return
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        act = 2 if blk.use_hs else 1
-        M = B * 7
-        self._linear(xin, self.C, blk.pWe, blk.be, self.h, self.E, M, self.C, self.E, act=act)           # expand+BN+act
-        self._lib.check(L.azg_nn_dw_pool(p(self.h), self.E, p(blk.Wd), p(blk.sd), p(blk.bd), p(self.pooled), B, self.E,
-                                         act, 0 if blk.setype == 'avg' else 1, self._stream()))           # depthwise+BN+act+squeeze
-        self._linear(self.pooled, self.E, blk.pW1, blk.b1, self.se_h, 48, B, self.E, self.Q, act=1, ksplit=1)   # SE fc1+ReLU
-        self._linear(self.se_h, 48, blk.pW2, blk.b2, self.sc, self.E, B, 48, self.E, act=3, ksplit=1)            # SE fc2+Hardsigmoid
-        self._linear(self.h, self.E, blk.pWp, blk.bp, xout, self.C, M, self.E, self.C, act=0, R=xin, ldr=self.C,
-                     rowscale=self.sc, rpg=7)                                                             # SE*h @ Wp + BN + residual
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        L = self._lib.lib()
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda
-        valids = valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)
-        if self.fused_net and self.h2:
-            self._lib.check(L.azg_nn_v80_forward_h2(p(boards), p(valids), self.net_ptrs_h2, self.descale_h2, B, self.P, p(self.pi), p(self.v),
-                                                    self._stream()))
-            return self.pi[:B], self.v[:B]
-        if self.fused_net:
-            fwd, ptrs = (L.azg_nn_v80_forward_split, self.net_ptrs_split) if self.split else (L.azg_nn_v80_forward, self.net_ptrs)
-            self._lib.check(fwd(p(boards), p(valids), ptrs, B, self.P, p(self.x2), p(self.pi), p(self.v), self._stream()))
-            return self.pi[:B], self.v[:B]
-        self._lib.check(L.azg_nn_board_to_x(p(boards), p(self.x0), B, self.C, self._stream()))
-        self._linear(self.x0, self.C, self.pW0, self.b0, self.x1, self.C, B * 7, self.C, self.C)           # first_layer
-        self._block(self.trunk, self.x1, self.x2, B)
-        self._block(self.head_pi, self.x2, self.xh, B)
-        self._linear(self.xh, 7 * self.C, self.pWpi1, self.bpi1, self.hid_pi, 96, B, 7 * self.C, self.A, act=1, ksplit=1)
-        self._linear(self.hid_pi, 96, self.pWpi2, self.bpi2, self.logits, 96, B, 96, self.A, ksplit=1)
-        self._block(self.head_v, self.x2, self.xh, B)
-        self._linear(self.xh, 7 * self.C, self.pWv1, self.bv1, self.hid_v, 16, B, 7 * self.C, self.P, ksplit=1)
-        self._lib.check(L.azg_nn_heads_out(p(self.logits), 96, p(valids), p(self.hid_v), 16, p(self.Wv2), p(self.bv2),
-                                           p(self.pi), p(self.v), B, self.A, self.P, self._stream()))
-        return self.pi[:B], self.v[:B]
-
+        fwd, ptrs = (L.azg_nn_v80_forward_split, self.net_ptrs_split) if self.split else (L.azg_nn_v80_forward, self.net_ptrs)
+        self._lib.check(fwd(boards, valids, ptrs, B, self.P, _ptr(self.pi), _ptr(self.v), stream))
 
 
 class AzulV84(SplendorV80):
@@ -560,17 +452,14 @@ MB1D_GEOMETRY = {(7, 56): 0, (7, 71): 1, (7, 88): 2, (6, 23): 3, (2, 58): 4, (15
 
 
 class MobileNet1dHip(_EngineNet):
-    """The MobileNetV3-1d policy/value nets of any geometry (Splendor V80 for 2-4 players: C = 32 + 10n + n^2 channels x 7
-    tokens; Azul V84: 23 channels x 6 tokens, AzulNNet.py:91-113) evaluated by the engine's gfx950 kernels instead of ~65
-    torch ops per leaf batch: azg_nn_board_to_x_ld, then per InvertedResidual1d block (SplendorNNet.py:189-202) expand GEMM
-    (bias + activation fused), depthwise+BN+act+squeeze, the two SE GEMMs and the project GEMM (SE scale on the operand,
-    bias, residual fused); flatten->Linear heads through the K-split GEMM; masked softmax / tanh tail.  17 launches.
-    Wraps a SplendorV80 / AzulV84 instance (folded-BN fp32 weights); channel counts are zero-padded to multiples of 4
-    (row strides) and of 16 (weight tiles), which leaves the results unchanged."""
-
-    _WS_CHUNKS = (1, 2, 3, 4, 6, 8, 11, 17, 25)
+    """The MobileNetV3-1d policy/value nets of any geometry in MB1D_GEOMETRY (Splendor V80 for 2-4 players: C = 32 + 10n + n^2 channels x 7
+    tokens; Azul V84: 23 channels x 6 tokens, AzulNNet.py:91-113; Minivilles V82; The Little Prince V83) evaluated by one launch of the
+    engine's gfx950 kernel (azg_nn_mb1d_forward / _h2, csrc/nn_mb1d.hip.h) instead of ~65 torch ops per leaf batch.  Wraps a SplendorV80 /
+    AzulV84 / MobileNet1d instance (folded-BN fp32 weights); matrices are zero-padded to multiples of 16 (K to 32 for the f16 x 2
+    operands) and stored in MFMA fragment order, which leaves the results unchanged."""
 
     def __init__(self, base, max_batch=4096, fused=True, h2=True):
+        """h2 (default): the GEMM phases on f16 x 2 split-precision operands (azg_nn_mb1d_forward_h2); False = f32 MFMAs throughout"""
         from . import _lib
         self._lib = _lib
         self.base = base
@@ -579,171 +468,58 @@ class MobileNet1dHip(_EngineNet):
         self.P, self.A, self.C = base.P, base.A, base.nb_vect
         self.L = getattr(base, 'L', 7)
         self.nb_vect = base.nb_vect
-        assert base.dtype == torch.float32 and self.device.type == 'cuda'
-        r4, r16 = (lambda n: (n + 3) // 4 * 4), (lambda n: (n + 15) // 16 * 16)
-        self.Cp = r4(self.C)
-        d = self.device
-
-        def padw(W, Kp, NP):
-            out = torch.zeros((Kp, NP), dtype=torch.float32, device=d)
-            out[:W.shape[0], :W.shape[1]] = W
-            return out
-
-        def padv(v, n):
-            out = torch.zeros(n, dtype=torch.float32, device=d)
-            out[:v.numel()] = v
-            return out
-        self.pW0, self.pb0 = padw(base.W0, r16(self.Cp), r16(self.C)), padv(base.b0, r16(self.C))
-        self.blocks = []
-        for blk in (base.trunk, base.head_pi, base.head_v):
-            cin, E = blk.We.shape
-            Q, cout = blk.W1.shape[1], blk.Wp.shape[1]
-            g = dict(cin=cin, cinp=r4(cin), E=E, Ep=r4(E), Q=Q, Qp=r16(Q), cout=cout, coutp=r4(cout), act=2 if blk.use_hs else 1,
-                     pool_max=0 if blk.setype == 'avg' else 1, res=cin == cout)
-            g['We'], g['be'] = padw(blk.We, r16(g['cinp']), r16(g['Ep'])), padv(blk.be, r16(g['Ep']))
-            g['Wd'], g['sd'], g['bd'] = blk.Wd.contiguous(), padv(blk.sd, g['Ep']), padv(blk.bd, g['Ep'])
-            g['W1'], g['b1'] = padw(blk.W1, r16(g['Ep']), g['Qp']), padv(blk.b1, g['Qp'])
-            g['W2'], g['b2'] = padw(blk.W2, g['Qp'], r16(g['Ep'])), padv(blk.b2, r16(g['Ep']))
-            g['Wp'], g['bp'] = padw(blk.Wp, r16(g['Ep']), r16(cout)), padv(blk.bp, r16(cout))
-            self.blocks.append(g)
-        L = self.L
-
-        def flat(W, cout, coutp):          # rows l*cout + c  ->  l*coutp + c (pad rows zero), then tile padding
-            N = W.shape[1]
-            w = torch.zeros((L, coutp, N), dtype=torch.float32, device=d)
-            w[:, :cout] = W.view(L, cout, N)
-            return padw(w.view(L * coutp, N), r16(L * coutp), r16(N))
-        gp, gv = self.blocks[1], self.blocks[2]
-        self.Ap = r16(self.A)
-        self.pWpi1, self.pWpi2 = flat(base.Wpi1, gp['cout'], gp['coutp']), padw(base.Wpi2, self.Ap, self.Ap)
-        self.pWv1 = flat(base.Wv1, gv['cout'], gv['coutp'])
-        self.bpi1, self.bpi2, self.bv1 = base.bpi1.contiguous(), base.bpi2.contiguous(), base.bv1.contiguous()
-        self.Wv2, self.bv2 = base.Wv2.contiguous(), base.bv2.contiguous()
+        self.S = self.C * self.L
         self.geometry = MB1D_GEOMETRY.get((self.L, self.C))
-        self.fused = fused and self.geometry is not None
-        if not self.fused and self.geometry not in (0, 1, 2, 3):
-            # the launch-per-layer path (azg_nn_linear's tile shapes) exists for the Splendor and Azul geometries only
-            raise ValueError('MobileNet1dHip: geometry L=%d C=%d has the one-launch kernels only (fused=True)' % (self.L, self.C))
-        if self.fused:
-            self._pack_fused(padw, padv, r16)
+        if not fused or self.geometry is None:
+            raise ValueError('MobileNet1dHip: the one-launch kernels are the only form (fused=True, a geometry of MB1D_GEOMETRY); got '
+                             'fused=%r, L=%d C=%d' % (fused, self.L, self.C))
+        self.fused = True              # the one-launch forward is the only form there is (tests and tools read this)
+        assert base.dtype == torch.float32 and self.device.type == 'cuda'
+        self._pack()
         self._alloc(max_batch)
 
-    def _pack_fused(self, padw, padv, r16):
+    def _pack(self):
         """the 43 weight pointers of azg_nn_mb1d_forward: matrices zero-padded to multiples of 16 and stored in MFMA
         fragment order, vectors zero-padded to multiples of 16"""
-        base, L, frag = self.base, self.L, SplendorV80Hip._frag
-        fw = lambda W: frag(padw(W, r16(W.shape[0]), r16(W.shape[1])))  # noqa: E731
+        base, L, r16 = self.base, self.L, _r16
+        padv = lambda v, n: _pad(v, (n,))  # noqa: E731
+        fw = lambda W: _frag(_pad(W, (r16(W.shape[0]), r16(W.shape[1]))))  # noqa: E731
         keep = [fw(base.W0), padv(base.b0, r16(self.C))]
         for blk in (base.trunk, base.head_pi, base.head_v):
             E, Q, co = blk.We.shape[1], blk.W1.shape[1], blk.Wp.shape[1]
             keep += [fw(blk.We), padv(blk.be, r16(E)), blk.Wd.contiguous(), padv(blk.sd, r16(E)), padv(blk.bd, r16(E)),
                      fw(blk.W1), padv(blk.b1, r16(Q)), fw(blk.W2), padv(blk.b2, r16(E)), fw(blk.Wp), padv(blk.bp, r16(co))]
-        co_pi, co_v = base.head_pi.Wp.shape[1], base.head_v.Wp.shape[1]
-        OS = r16(max(self.C, co_pi)) + 4
-
-        def flat(W, cout):                 # rows l*cout + c -> l*OS + c
-            w = torch.zeros((L, OS, W.shape[1]), dtype=torch.float32, device=W.device)
-            w[:, :cout] = W.view(L, cout, W.shape[1])
-            return fw(w.view(L * OS, W.shape[1]))
-        keep += [flat(base.Wpi1, co_pi), padv(base.bpi1, r16(self.A)), fw(base.Wpi2), padv(base.bpi2, r16(self.A)),
-                 flat(base.Wv1, co_v), padv(base.bv1, 16), base.Wv2.contiguous(), base.bv2.contiguous()]
+        OS = r16(max(self.C, base.head_pi.Wp.shape[1])) + 4             # row stride of the kernel's output tile: row k = l*OS + c
+        wpi1, wv1 = _flat_rows(base.Wpi1, L, OS), _flat_rows(base.Wv1, L, OS)
+        keep += [fw(wpi1), padv(base.bpi1, r16(self.A)), fw(base.Wpi2), padv(base.bpi2, r16(self.A)),
+                 fw(wv1), padv(base.bv1, 16), base.Wv2.contiguous(), base.bv2.contiguous()]
         assert len(keep) == 43
         self._fused_keep = keep
         self.fused_ptrs = (C.c_void_p * 43)(*[t.data_ptr() for t in keep])
         # azg_nn_mb1d_forward_h2: the same table with the matrices as f16 x 2 fragments (K padded to multiples of 32)
-        r32 = lambda n: (r16(n) + 31) // 32 * 32  # noqa: E731
         desc = []
 
         def fh(W):
             k = _pow2_scale(W.abs().max())
             desc.append(_descale(k))
-            return _split_frag(padw(W, r32(W.shape[0]), r16(W.shape[1])), 'h2', k)
-
-        def flat_rows(W, cout):
-            w = torch.zeros((L, OS, W.shape[1]), dtype=torch.float32, device=W.device)
-            w[:, :cout] = W.view(L, cout, W.shape[1])
-            return w.view(L * OS, W.shape[1])
+            return _split_frag(_pad(W, ((r16(W.shape[0]) + 31) // 32 * 32, r16(W.shape[1]))), 'h2', k)
         k2 = list(keep)
         k2[0] = fh(base.W0)
         for b, blk in enumerate((base.trunk, base.head_pi, base.head_v)):
             o = 2 + 11 * b
             k2[o], k2[o + 5], k2[o + 7], k2[o + 9] = fh(blk.We), fh(blk.W1), fh(blk.W2), fh(blk.Wp)
-        k2[35], k2[37], k2[39] = fh(flat_rows(base.Wpi1, co_pi)), fh(base.Wpi2), fh(flat_rows(base.Wv1, co_v))
+        k2[35], k2[37], k2[39] = fh(wpi1), fh(base.Wpi2), fh(wv1)
         assert len(desc) == 16
         self._fused_keep_h2 = k2
         self.fused_ptrs_h2 = (C.c_void_p * 43)(*[t.data_ptr() for t in k2])
         self.descale_h2 = (C.c_float * 16)(*desc)
 
-    def _alloc(self, B):
-        d, f = self.device, torch.float32
-        self.maxB = B
-        M = B * self.L
-        z = lambda *shape: torch.zeros(shape, dtype=f, device=d)  # noqa: E731   (pad columns must stay zero)
-        self.x0, self.x1, self.x2 = z(M, self.Cp), z(M, self.Cp), z(M, self.blocks[0]['coutp'])
-        Epm, Qpm = max(g['Ep'] for g in self.blocks), max(g['Qp'] for g in self.blocks)
-        self.h, self.pooled, self.sc, self.se_h = z(M * Epm), z(B * Epm), z(B * Epm), z(B * Qpm)
-        self.xh_pi, self.xh_v = z(M * self.blocks[1]['coutp']), z(M * self.blocks[2]['coutp'])
-        self.hid_pi, self.logits, self.hid_v = z(B, self.Ap), z(B, self.Ap), z(B, 16)
-        self.pi = torch.empty((B, self.A), dtype=f, device=d)
-        self.v = torch.empty((B, self.P), dtype=f, device=d)
-
-    def _lin(self, A, lda, Wp, bias_p, out, ldc, M, K, N, act=0, R=None, ldr=0, rowscale=None, rpg=0, ksplit=False):
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    def _launch(self, boards, valids, B, stream):
         L = self._lib.lib()
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        Kp, NP = Wp.shape
-        if not ksplit and Kp // 16 in self._WS_CHUNKS:
-            self._lib.check(L.azg_nn_linear_ws(p(A), lda, p(Wp), Kp, NP, p(bias_p), p(R), ldr, p(rowscale), rpg, p(out), ldc,
-                                               M, K, N, act, st))
+        if self.h2:
+            self._lib.check(L.azg_nn_mb1d_forward_h2(self.geometry, boards, valids, self.fused_ptrs_h2, self.descale_h2, B, _ptr(self.pi), _ptr(self.v), stream))
         else:
-            self._lib.check(L.azg_nn_linear(p(A), lda, p(Wp), Kp, NP, p(bias_p), p(R), ldr, p(rowscale), rpg, p(out), ldc,
-                                            M, K, N, act, 1 if ksplit else 0, st))
-
-    def _block(self, g, xin, xout, B):
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        M, Ep = B * self.L, g['Ep']
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self._lin(xin, g['cinp'], g['We'], g['be'], self.h, Ep, M, g['cinp'], Ep, act=g['act'])
-        self._lib.check(self._lib.lib().azg_nn_dw_pool_l(p(self.h), Ep, p(g['Wd']), p(g['sd']), p(g['bd']), p(self.pooled), B,
-                                                         Ep, self.L, g['act'], g['pool_max'], st))
-        self._lin(self.pooled, Ep, g['W1'], g['b1'], self.se_h, g['Qp'], B, Ep, g['Q'], act=1)
-        self._lin(self.se_h, g['Qp'], g['W2'], g['b2'], self.sc, Ep, B, g['Qp'], Ep, act=3)
-        self._lin(self.h, Ep, g['Wp'], g['bp'], xout, g['coutp'], M, Ep, g['cout'], R=xin if g['res'] else None,
-                  ldr=g['cinp'], rowscale=self.sc, rpg=self.L)
-
-    @torch.no_grad()
-    def forward(self, boards, valids):
-        B = boards.shape[0]
-        if B > self.maxB:
-            self._alloc(B)
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        Lb = self._lib.lib()
-        st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        boards = boards.reshape(B, -1)
-        assert boards.dtype == torch.int8 and boards.is_contiguous() and boards.is_cuda
-        valids = valids if valids.dtype == torch.uint8 else valids.to(torch.uint8)
-        if self.fused:                                  # the whole forward in one launch (nn_mb1d.hip.h)
-            if self.h2:
-                self._lib.check(Lb.azg_nn_mb1d_forward_h2(self.geometry, p(boards), p(valids.contiguous()), self.fused_ptrs_h2,
-                                                          self.descale_h2, B, p(self.pi), p(self.v), st))
-            else:
-                self._lib.check(Lb.azg_nn_mb1d_forward(self.geometry, p(boards), p(valids.contiguous()), self.fused_ptrs, B,
-                                                       p(self.pi), p(self.v), st))
-            return self.pi[:B], self.v[:B]
-        self._lib.check(Lb.azg_nn_board_to_x_ld(p(boards), p(self.x0), B, self.C, self.L, self.Cp, st))
-        self._lin(self.x0, self.Cp, self.pW0, self.pb0, self.x1, self.Cp, B * self.L, self.Cp, self.C)       # first_layer
-        gt, gp, gv = self.blocks
-        self._block(gt, self.x1, self.x2, B)
-        self._block(gp, self.x2, self.xh_pi, B)
-        Kp1 = self.L * gp['coutp']
-        self._lin(self.xh_pi, Kp1, self.pWpi1, self.bpi1, self.hid_pi, self.Ap, B, Kp1, self.A, act=1, ksplit=True)
-        self._lin(self.hid_pi, self.Ap, self.pWpi2, self.bpi2, self.logits, self.Ap, B, self.Ap, self.A, ksplit=True)
-        self._block(gv, self.x2, self.xh_v, B)
-        Kv1 = self.L * gv['coutp']
-        self._lin(self.xh_v, Kv1, self.pWv1, self.bv1, self.hid_v, 16, B, Kv1, self.P, ksplit=True)
-        self._lib.check(Lb.azg_nn_heads_out(p(self.logits), self.Ap, p(valids), p(self.hid_v), 16, p(self.Wv2), p(self.bv2),
-                                            p(self.pi), p(self.v), B, self.A, self.P, st))
-        return self.pi[:B], self.v[:B]
+            self._lib.check(L.azg_nn_mb1d_forward(self.geometry, boards, valids, self.fused_ptrs, B, _ptr(self.pi), _ptr(self.v), stream))
 
 
 class SantoriniV89(_TorchNet):
@@ -809,7 +585,7 @@ class SantoriniV89Hip(_EngineNet):
         self._lib, self.base, self.device, self.split, self.h2 = _lib, base, base.device, bool(split), bool(h2)
         self.P, self.A = base.P, base.A
         assert base.dtype == torch.float32 and self.device.type == 'cuda' and len(base.blocks) == 5 and self.A == 162 and self.P == 2
-        frag = SplendorV80Hip._frag
+        frag = _frag
         d = self.device
 
         def conv_rows(w):                  # [co][ci][3][3] -> [K = tap*64 + ci][co]
@@ -929,7 +705,7 @@ class SantoriniV78Hip(SantoriniV89Hip):
             # [4 ct][2 chunks of 32][planes][64 lanes][8]: f16 hi / lo of W * 2^k (h2) or bf16 hi / mid / lo
             kind, k = ('h2', kp if of_k else ke) if self.h2 else ('bf16x3', 0)
             return torch.cat([_split_frag(m[64 * t:64 * t + 64] if of_k else m[:, 64 * t:64 * t + 64], kind, k) for m in ms for t in range(3)]).contiguous()
-        frag = SplendorV80Hip._frag
+        frag = _frag
         d = self.device
         m0 = torch.zeros((9, 16, 64), dtype=torch.float32, device=d)
         m0[:, :2] = base.c0[0].permute(2, 3, 1, 0).reshape(9, 2, 64)

@@ -386,54 +386,30 @@ int azg_selfplay_drain_examples(azg_forest* f, int max_records, int8_t* boards_d
                                 uint8_t* valids_dev, float* q_dev, int32_t* meta_dev /* i32[n][4] = (global game
                                 stream, game index on it, ply, player) or NULL */, int* n_out, void* stream);
 
-/* ---- policy/value net building blocks: NeuralNet.predict for a whole leaf batch (NeuralNet.py:32-43,
-   GenericNNetWrapper.py:94-120; V80 network splendor/SplendorNNet.py:148-202,262-283,397-440), fp32 ----
-   out[M][N] = act(A'[M][K] @ W + bias) (+ R);  A' = A * rowscale[row / rows_per_group][k] when rowscale != NULL (fuses the
-   SqueezeExcitation multiply into the project GEMM).  Wp is the weight pre-padded with zeros to [Kp][NP], Kp = K rounded
-   up to 16, NP/16 in {1,4,6,11}.  act: 0 none, 1 ReLU, 2 Hardswish, 3 Hardsigmoid.  K, lda % 4 == 0.  ksplit = 1 selects the variant for
-   M ~ batch and long K (flatten->Linear heads).  MFMA v_mfma_f32_16x16x4_f32 (exact f32 == an fmaf chain). */
-int azg_nn_linear(const float* A_dev, int lda, const float* Wp_dev, int Kp, int NP, const float* bias_dev,
-                  const float* R_dev, int ldr, const float* rowscale_dev, int rows_per_group, float* out_dev, int ldc,
-                  int M, int K, int N, int act, int ksplit, void* stream);
-/* Same contract, weight-stationary kernel (weights in registers as the MFMA A operand, activations streamed as float4,
-   float4 epilogue, no LDS): the variant the V80 forward uses for every layer.  bias_padded: NP floats (zero padded) or
-   NULL; ldc (and ldr) % 4 == 0; Kp/16 in {1,3,4,6,11,25}. */
-int azg_nn_linear_ws(const float* A_dev, int lda, const float* Wp_dev, int Kp, int NP, const float* bias_padded_dev,
-                     const float* R_dev, int ldr, const float* rowscale_dev, int rows_per_group, float* out_dev, int ldc,
-                     int M, int K, int N, int act, void* stream);
-/* depthwise Linear(7->7) over the token axis + folded BatchNorm + activation, in place on H[B*7][ldh], and the SE squeeze
-   pooled[B][E] (mean or max over the 7 tokens)  (SplendorNNet.py:148-187).  The SE excitation
-   hardsigmoid(relu(pooled @ W1 + b1) @ W2 + b2) is two azg_nn_linear calls (act 1, then act 3 = Hardsigmoid). */
-int azg_nn_dw_pool(float* H_dev, int ldh, const float* Wd_dev /*[7][7] out,in*/, const float* bn_scale_dev,
-                   const float* bn_bias_dev, float* pooled_dev, int B, int E, int act, int pool_max, void* stream);
-/* the same for L tokens per sample (7: Splendor boards [C][7]; 6: Azul boards [23][6], AzulNNet.py:91-113) */
-int azg_nn_dw_pool_l(float* H_dev, int ldh, const float* Wd_dev /*[L][L] out,in*/, const float* bn_scale_dev,
-                     const float* bn_bias_dev, float* pooled_dev, int B, int E, int L, int act, int pool_max, void* stream);
-/* One fused InvertedResidual1d block of the V80 net (SplendorNNet.py:189-202: expand + depthwise + SE + project +
-   residual) for x[B*7][56] -> out[B*7][56]; the 168-wide expanded activations stay in LDS.  w = 11 HOST-array device
-   pointers {We[64][176], be[176], Wd[7][7], bn_scale[168], bn_bias[168], W1[176][48], b1[48], W2[48][176], b2[176],
-   Wp[176][64], bp[64]} (zero padded, BatchNorm folded).  The four matrices are stored in MFMA fragment order:
-   frag[n/16][k/16][lane 0..63][j 0..3] = W[16*(k/16) + 4*(lane>>4) + j][16*(n/16) + (lane&15)] (one 1 KiB load per wave and
-   K chunk).  act 1 ReLU / 2 Hardswish; pool_max 0 mean / 1 max. */
-int azg_nn_v80_block(const float* xin_dev, float* xout_dev, const float* const* w, int B, int act, int pool_max,
-                     void* stream);
+/* ---- policy/value nets: NeuralNet.predict for a whole leaf batch, every net in one launch (NeuralNet.py:32-43,
+   GenericNNetWrapper.py:94-120; V80 network splendor/SplendorNNet.py:148-202,262-283,397-440) ---- */
 /* The whole V80 forward (NeuralNet.predict for a leaf batch, SplendorNNet.py:397-440 / GenericNNetWrapper.py:94-110) in
    ONE launch, one workgroup pass per 16 samples: boards int8[B][56][7] -> first_layer + trunk block (output kept in LDS,
    two copies) -> policy head block + Flatten + Linear + ReLU + Linear + masked softmax -> pi f32[B][81]; value head block
-   + Flatten + Linear + ReLU + Linear + tanh -> v f32[B][P].  x_trunk (f32 [B*7][56]) is only written by the three-launch
-   variant (environment AZG_NN_THREE_LAUNCHES=1, kept for A/B measurements).  w = 43 device pointers: {W0[64][64], b0[64]}, 3 x the 11 block tensors of
-   azg_nn_v80_block (trunk, policy head, value head), {Wpi1[432][96], bpi1[96], Wpi2[96][96], bpi2[96]},
-   {Wv1[432][16], bv1[16], Wv2[P][P], bv2[P]}; the flatten index of Wpi1 / Wv1 rows is k = l*60 + c (c < 56), zero
-   padded; every matrix except Wv2 is in the fragment order described at azg_nn_v80_block.  Fixed to the V80 activations (trunk ReLU + mean squeeze, heads Hardswish + max squeeze). */
+   + Flatten + Linear + ReLU + Linear + tanh -> v f32[B][P].  f32 operands throughout: MFMA v_mfma_f32_16x16x4_f32 (exact f32
+   == an fmaf chain).  w = 43 device pointers: {W0[64][64], b0[64]}, 3 x the 11 tensors of an InvertedResidual1d block
+   (SplendorNNet.py:189-202: expand + depthwise + SE + project + residual; trunk, policy head, value head)
+   {We[64][176], be[176], Wd[7][7], bn_scale[168], bn_bias[168], W1[176][48], b1[48], W2[48][176], b2[176], Wp[176][64],
+   bp[64]}, {Wpi1[432][96], bpi1[96], Wpi2[96][96], bpi2[96]}, {Wv1[432][16], bv1[16], Wv2[P][P], bv2[P]}; zero padded,
+   BatchNorm folded; the flatten index of Wpi1 / Wv1 rows is k = l*60 + c (c < 56).  Every matrix except Wd / Wv2 is stored in
+   MFMA fragment order: frag[n/16][k/16][lane 0..63][j 0..3] = W[16*(k/16) + 4*(lane>>4) + j][16*(n/16) + (lane&15)] (one 1 KiB
+   load per wave and K chunk); where K = 8 mod 16 (W0, We, W1, Wp) the last chunk holds its 8 rows as
+   W[16*(k/16) + 2*(lane>>4) + j] in j = 0, 1.  Fixed to the V80 activations (trunk ReLU + mean squeeze, heads Hardswish + max
+   squeeze). */
 int azg_nn_v80_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int B, int P,
-                       float* x_trunk_dev, float* pi_dev, float* v_dev, void* stream);
+                       float* pi_dev, float* v_dev, void* stream);
 /* The same forward with the expand GEMM of the three blocks on split-precision operands (every f32 value as three bf16 numbers
    hi + mid + lo, a product = the six bf16 MFMAs of relative weight >= 2^-24; f32-input MFMA runs at 1/16 of the bf16 rate on
    gfx950): the tile the blocks read lives in LDS as three bf16 planes, written split once by the producing epilogue; one copy of
    the trunk output serves both heads.  Only We (w[2], w[13], w[24]) differs: [11 column tiles][2 K chunks of 32][3 planes]
    [64 lanes][8] bf16 with element = W_plane[32*chunk + 8*(lane>>4) + j][16*tile + (lane&15)], K zero padded 56 -> 64. */
 int azg_nn_v80_forward_split(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int B, int P,
-                             float* x_trunk_dev, float* pi_dev, float* v_dev, void* stream);
+                             float* pi_dev, float* v_dev, void* stream);
 /* The same forward (NeuralNet.predict for a leaf batch, SplendorNNet.py:397-440 / GenericNNetWrapper.py:94-110) on fp16 hi+lo
    split operands (every f32 weight / activation as hi = rn16(x), lo = rn16(x - hi): 22 significant bits; a product = three
    v_mfma_f32_16x16x32_f16) with TOKEN-MAJOR tiles, so that the depthwise token mix, its BN + activation, the squeeze and the SE
@@ -591,14 +567,6 @@ int azg_nn_akr31_forward(const int8_t* boards_dev, const uint8_t* valid_dev, con
    Same 1e-5 contract as the torch net.  n_mach must be 1 or 2, P 2, A 428. */
 int azg_nn_bot_forward(const int8_t* boards_dev, const uint8_t* valid_dev, const float* const* w, int n_mach, int P, int A, int B,
                        float* pi_dev, float* v_dev, void* stream);
-/* boards int8 [B][C][7] (reference board layout) -> x f32 [B][7][C] */
-int azg_nn_board_to_x(const int8_t* boards_dev, float* x_dev, int B, int C, void* stream);
-/* boards int8 [B][C][L] -> x f32 [B][L][ldx], columns C..ldx-1 zeroed (row stride padded to a multiple of 4 floats) */
-int azg_nn_board_to_x_ld(const int8_t* boards_dev, float* x_dev, int B, int C, int L, int ldx, void* stream);
-/* pi = softmax(where(valid, logits, -1e8)) (== exp(log_softmax), GenericNNetWrapper.py:107); v = tanh(relu(vhid) @ Wv2 + bv2) */
-int azg_nn_heads_out(const float* logits_dev, int ldl, const uint8_t* valid_dev, const float* vhid_dev, int ldv,
-                     const float* Wv2_dev, const float* bv2_dev, float* pi_dev, float* v_dev, int B, int A, int P,
-                     void* stream);
 
 /* ---- measurement helpers ---- */
 /* time `iters` back-to-back launches of kernel `which` (0 = select, 1 = expand_backup) with hipEvents on `stream`

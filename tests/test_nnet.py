@@ -57,16 +57,15 @@ def test_v80_forward_gpu():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('path', ['fused_net_h2', 'fused_net', 'fused_net_f32', 'fused_blocks', 'unfused'])
+@pytest.mark.parametrize('path', ['fused_net_h2', 'fused_net', 'fused_net_f32'])
 def test_v80_hip_kernels_forward_gpu(path):
-    """The engine's own gfx950 net kernels vs the reference model's outputs: the 3-launch whole-net fusion
-    (azg_nn_v80_forward), the per-block fusion (azg_nn_v80_block + skinny GEMMs) and the unfused kernel chain."""
+    """The engine's own gfx950 net kernels vs the reference model's outputs: the one-launch forward on fp16 hi+lo operands with
+    token-major tiles (azg_nn_v80_forward_h2, the default), with the expand GEMMs on bf16 x 3 operands (azg_nn_v80_forward_split)
+    and on f32 MFMAs throughout (azg_nn_v80_forward)."""
     from azg_amd.nnet import SplendorV80Hip, SplendorV80
     root = os.path.join(os.path.dirname(__file__), 'golden')
     net = SplendorV80Hip.from_npz(os.path.join(root, 'weights_splendor2_v80.npz'), device='cuda:0', max_batch=512, split=path != 'fused_net_f32',
                                   h2=path == 'fused_net_h2')
-    net.fused_net = path.startswith('fused_net')      # one launch: fp16 hi+lo operands on token-major tiles (default), bf16 x 3 expand, or f32 MFMAs throughout
-    net.fused_blocks = path != 'unfused'
     d = np.load(os.path.join(root, 'netfwd_splendor2_v80.npz'))
     boards = torch.from_numpy(d['boards']).cuda()
     masks = torch.from_numpy(d['masks']).cuda()
@@ -211,11 +210,21 @@ def test_v80_4p_forward_gpu():
     _check_v80_4p('cuda:0')
 
 
+def test_mobilenet1d_engine_has_the_one_launch_form_only():
+    """fused=False (the retired launch-per-layer chain) is refused when the evaluator is constructed, before anything touches a GPU"""
+    from azg_amd import nnet
+    root = os.path.join(os.path.dirname(__file__), 'golden')
+    for cls, tag in (('AzulV84', 'azul_v84'), ('MobileNet1d', 'minivilles2_v82')):
+        base = getattr(nnet, cls).from_npz(os.path.join(root, 'weights_%s.npz' % tag), device='cpu')
+        with pytest.raises(ValueError):
+            nnet.MobileNet1dHip(base, max_batch=64, fused=False)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize('fused', [False, True, 'h2'], ids=['launches17', 'fused_f32', 'fused_h2'])
+@pytest.mark.parametrize('fused', [True, 'h2'], ids=['fused_f32', 'fused_h2'])
 @pytest.mark.parametrize('tag', ['splendor2_v80', 'splendor4_v80', 'azul_v84', 'minivilles2_v82', 'tlp3_v83'])
 def test_mobilenet1d_engine_kernels_gpu(tag, fused):
-    """MobileNet1dHip (engine GEMM / depthwise / head kernels, any geometry) vs the reference models' golden outputs, and at
+    """MobileNet1dHip (the one-launch engine kernel, any geometry) vs the reference models' golden outputs, and at
     a batch that is not a multiple of the 16-row tiles vs the torch-ops evaluation of the same weights."""
     from azg_amd import nnet
     root = os.path.join(os.path.dirname(__file__), 'golden')
@@ -226,11 +235,7 @@ def test_mobilenet1d_engine_kernels_gpu(tag, fused):
     else:
         npl = 4 if tag.startswith('splendor4') else 2
         base = nnet.SplendorV80.from_npz(os.path.join(root, 'weights_%s.npz' % tag), num_players=npl, device='cuda:0')
-    if not fused and tag in ('minivilles2_v82', 'tlp3_v83'):
-        with pytest.raises(ValueError):            # the launch-per-layer path exists for the Splendor / Azul geometries only
-            nnet.MobileNet1dHip(base, max_batch=64, fused=False)
-        return
-    # one launch with the GEMM phases on f16 x 2 split-precision operands (default) / on f32 MFMAs / 17 launches
+    # one launch with the GEMM phases on f16 x 2 split-precision operands (default) / on f32 MFMAs
     net = nnet.MobileNet1dHip(base, max_batch=64, fused=bool(fused), h2=fused == 'h2')
     assert net.fused == bool(fused)
     d = np.load(os.path.join(root, 'netfwd_%s.npz' % tag))

@@ -29,7 +29,6 @@ for tag, mk, shape, A in [('splendor2', lambda: nnet.SplendorV80.from_npz(G + '/
     valids = (torch.rand((T, A), device='cuda:0') < 0.5).to(torch.uint8)
     valids[:, -1] = 1
     row = {'torch ops': timed(base, boards, valids.bool(), 10),
-           '17 launches': timed(nnet.MobileNet1dHip(base, max_batch=T, fused=False), boards, valids),
            'k_mb1d_net f32': timed(nnet.MobileNet1dHip(base, max_batch=T, fused=True, h2=False), boards, valids),
            'k_mb1d_net h2': timed(nnet.MobileNet1dHip(base, max_batch=T, fused=True, h2=True), boards, valids)}
     if tag == 'splendor2':
