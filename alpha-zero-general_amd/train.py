@@ -5,6 +5,9 @@
 azg_amd.nnet (which fold its BatchNorms).  `train()` is GenericNNetWrapper.train (:44-92): AdamW + OneCycleLR,
 loss = KLDiv(pi) + 0.25 * MSE((z + q_weight*q) / (1 + q_weight)) (:179-190), batches sampled without replacement inside a
 batch, `epochs * (len(examples) // batch_size)` steps."""
+import ctypes as C
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -471,14 +474,110 @@ def loss_v(target_z, target_q, out_v, q_weight):                               #
     return torch.sum((t - out_v) ** 2) / (target_z.shape[0] * target_z.shape[-1])
 
 
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def sample_ids(n, batch, n_steps, rng_seed, stream0=0, device='cuda:0', out=None):
+    """azg_train_sample_ids (include/azg.h; csrc/train.hip.h): np.random.choice(n, batch, replace=False) for n_steps steps in ONE launch
+    -> int32[n_steps, batch] on `device`.  Row s is the Fisher-Yates draw of the RNG contract's stream (rng_seed, stream0 + s); nothing is
+    synchronised.  out: an int32[n_steps, batch] CUDA tensor to fill instead of a new one."""
+    from . import _lib
+    if out is None:
+        out = torch.empty((max(int(n_steps), 0), max(int(batch), 0)), dtype=torch.int32, device=device)
+    assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == (n_steps, batch) and out.is_contiguous(), \
+        'sample_ids: out must be a contiguous int32[n_steps, batch] CUDA tensor'
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().azg_train_sample_ids(int(n), int(batch), int(n_steps), int(rng_seed) & (2 ** 64 - 1), int(stream0) & (2 ** 64 - 1),
+                                                   _ptr(out), _stream()))
+    return out
+
+
+def gather_batch(cols, ids, out=None):
+    """azg_train_gather: rows `ids` (int32[B], CUDA) of the five example columns cols = (boards int8[n, S], pi f32[n, A], z f32[n, P], valids
+    u8[n, A], q f32[n, P]), contiguous CUDA tensors, in one launch -> (boards int8[B, S], pi, z, valids u8[B, A] holding 0 / 1 -- view it as
+    torch.bool --, q).  An id outside [0, n) gives an undefined row.  out: five tensors to fill instead of new ones."""
+    from . import _lib
+    boards, pi, z, valids, q = cols
+    n, S = boards.shape
+    A, P, B = pi.shape[1], z.shape[1], ids.shape[0]
+    for x, dt, shape in ((boards, torch.int8, (n, S)), (pi, torch.float32, (n, A)), (z, torch.float32, (n, P)), (valids, torch.uint8, (n, A)),
+                         (q, torch.float32, (n, P)), (ids, torch.int32, (B,))):
+        assert x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous() and x.device == boards.device, \
+            'gather_batch: dtype / shape / layout of an argument'
+    if out is None:
+        out = tuple(torch.empty((B, x.shape[1]), dtype=x.dtype, device=x.device) for x in cols)
+    for o, x in zip(out, cols):
+        assert o.dtype == x.dtype and tuple(o.shape) == (B, x.shape[1]) and o.is_contiguous() and o.device == x.device, \
+            'gather_batch: dtype / shape / layout of an output'
+    with torch.cuda.device(boards.device):
+        _lib.check(_lib.lib().azg_train_gather(_ptr(boards), _ptr(pi), _ptr(z), _ptr(valids), _ptr(q), _ptr(ids), n, B, S, A, P,
+                                               *[_ptr(o) for o in out], _stream()))
+    return tuple(out)
+
+
+def train_losses(log_pi, v, target_pi, z, q, q_weight, v_coeff=0.25, out=None):
+    """azg_train_losses on contiguous f32 CUDA tensors (log_pi / target_pi [B, A], v / z / q [B, P]) -> (grad_log_pi f32[B, A], grad_v
+    f32[B, P], rows f64[B, 2], out f64[2]): the row sums and the totals (loss_pi, loss_v) of include/azg.h, and the gradient of loss_pi +
+    v_coeff * loss_v with respect to log_pi and v.  The buffers are allocated here (out too when None): the C call owns no memory.  Two
+    launches on the current stream, nothing synchronised."""
+    from . import _lib
+    B, A = log_pi.shape
+    P = v.shape[1]
+    for x, shape in ((log_pi, (B, A)), (target_pi, (B, A)), (v, (B, P)), (z, (B, P)), (q, (B, P))):
+        assert x.is_cuda and x.dtype == torch.float32 and tuple(x.shape) == shape and x.is_contiguous() and x.device == log_pi.device, \
+            'train_losses: dtype / shape / layout of an argument'
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=log_pi.device)
+    assert out.dtype == torch.float64 and tuple(out.shape) == (2,) and out.is_contiguous() and out.device == log_pi.device, \
+        'train_losses: out must be a contiguous f64[2] tensor on the same device'
+    g_pi, g_v = torch.empty_like(log_pi), torch.empty_like(v)
+    rows = torch.empty((B, 2), dtype=torch.float64, device=log_pi.device)
+    with torch.cuda.device(log_pi.device):
+        _lib.check(_lib.lib().azg_train_losses(_ptr(log_pi), _ptr(v), _ptr(target_pi), _ptr(z), _ptr(q), B, A, P, C.c_float(float(q_weight)),
+                                               C.c_float(float(v_coeff)), _ptr(g_pi), _ptr(g_v), _ptr(rows), _ptr(out), _stream()))
+    return g_pi, g_v, rows, out
+
+
+class _FusedLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_pi, v, target_pi, z, q, q_weight, v_coeff, out):
+        g_pi, g_v, _, out = train_losses(log_pi.contiguous(), v.contiguous(), target_pi, z, q, q_weight, v_coeff, out)
+        ctx.save_for_backward(g_pi, g_v)
+        return (out[0] + float(v_coeff) * out[1]).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        g_pi, g_v = ctx.saved_tensors
+        return g_pi * grad_output, g_v * grad_output, None, None, None, None, None, None
+
+
+def fused_loss(log_pi, v, target_pi, z, q, q_weight, v_coeff=0.25, out=None):
+    """L = loss_pi(target_pi, log_pi) + v_coeff * loss_v(z, q, v, q_weight) as an f32 scalar with its backward pass, by azg_train_losses
+    (include/azg.h; csrc/train.hip.h): two launches forward, which also write the gradients with respect to log_pi and v; backward hands
+    them on, scaled by grad_output on the device.  log_pi f32[B, A] LOG-probabilities, v f32[B, P] (the module's outputs), target_pi
+    f32[B, A], z / q f32[B, P], all CUDA.  out: an f64[2] tensor that receives (loss_pi, loss_v) -- e.g. a row of a per-epoch buffer, read
+    once; a new one when None.  Nothing is synchronised."""
+    return _FusedLoss.apply(log_pi, v, target_pi, z, q, q_weight, v_coeff, out)
+
+
 def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=0.5, device='cuda:0', seed=None, log=None, board_shape=None,
-          on_step=None):
+          device_batches=False, batch_ids=None, on_step=None):
     """examples = (boards int8[n,S], pi f32[n,A], z f32[n,P], valids u8/bool[n,A], q f32[n,P]) tensors or arrays.
     board_shape: give it for a module that expects the reference's inputs (float boards of getBoardSize(), bool valids:
     GenericNNetWrapper.py:60-63) instead of the engine modules' flat int8 boards.
     on_step(epoch, i_batch, step): called after every optimiser + scheduler step (step = i_batch + steps_per_epoch * epoch) -- the hook of
     the reference's periodic validation (:86-90); it must leave the module in train() mode.  With None nothing changes, random stream included.
+    batch_ids: an int array [epochs * steps_per_epoch, batch_size]: row `step` is that step's batch instead of a draw (either path; the
+    generator is then not used).
+    device_batches=True (CUDA only): the batches never touch the host -- _train_device_batches.  With the defaults nothing changes.
     Returns the list of (pi loss, v loss) per step."""
+    if device_batches:
+        return _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids)
     boards, pi, z, valids, q = [torch.as_tensor(np.asarray(x.cpu()) if hasattr(x, 'cpu') else x).to(device) for x in examples[:5]]
     n = boards.shape[0]
     valids = valids.bool()
@@ -487,6 +586,8 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
     steps_per_epoch = n // batch_size
     if steps_per_epoch == 0:
         raise ValueError('fewer examples (%d) than batch_size (%d)' % (n, batch_size))
+    if batch_ids is not None:
+        batch_ids = _check_batch_ids(batch_ids, epochs * steps_per_epoch, batch_size).to(device)
     module.to(device).train()
     opt = torch.optim.AdamW(module.parameters(), lr=learn_rate)
     sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=learn_rate, steps_per_epoch=steps_per_epoch, epochs=epochs)
@@ -496,7 +597,10 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
     hist = []
     for ep in range(epochs):
         for i_batch in range(steps_per_epoch):
-            ids = torch.randperm(n, generator=gen)[:batch_size].to(device)   # np.random.choice(n, batch, replace=False) :57
+            if batch_ids is not None:
+                ids = batch_ids[i_batch + steps_per_epoch * ep]
+            else:
+                ids = torch.randperm(n, generator=gen)[:batch_size].to(device)   # np.random.choice(n, batch, replace=False) :57
             opt.zero_grad(set_to_none=True)
             out_pi, out_v = module(boards[ids], valids[ids])
             l_pi = loss_pi(pi[ids].float(), out_pi)
@@ -510,5 +614,67 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
         if log:
             log('epoch %d: pi loss %.4f  v loss %.4f' % (ep + 1, np.mean([h[0] for h in hist[-steps_per_epoch:]]),
                                                          np.mean([h[1] for h in hist[-steps_per_epoch:]])))
+    module.eval()
+    return hist
+
+
+def _check_batch_ids(batch_ids, steps, batch_size):
+    """-> int64 CPU tensor [steps, batch_size]"""
+    ids = torch.as_tensor(np.asarray(batch_ids.cpu()) if hasattr(batch_ids, 'cpu') else np.asarray(batch_ids))
+    if ids.dtype.is_floating_point or ids.dtype == torch.bool or tuple(ids.shape) != (steps, batch_size):
+        raise ValueError('batch_ids must be an int array [epochs * steps_per_epoch, batch_size] = [%d, %d], got %s %s'
+                         % (steps, batch_size, ids.dtype, tuple(ids.shape)))
+    return ids.long()
+
+
+def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids):
+    """train() with the batches drawn, gathered and scored on the GPU (csrc/train.hip.h): the columns are made contiguous on the device once;
+    one sample_ids launch draws an epoch's ids (rng_seed = seed, or fresh entropy when None; stream0 = epoch * steps_per_epoch); a step is
+    gather_batch, the module's forward, fused_loss, backward, opt.step(), sched.step(); the losses land in a device buffer f64[steps, 2]
+    that is read once per epoch.  The host waits for the GPU at the end of an epoch only (and wherever on_step does)."""
+    if torch.device(device).type != 'cuda':
+        raise ValueError('train: device_batches=True needs a CUDA device, got %r (there is no CPU form of the batch kernels)' % (device,))
+    dev = torch.device(device)
+    boards, pi, z, valids, q = [x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in examples[:5]]
+    n = int(boards.shape[0])
+    cols = (boards.to(dev).reshape(n, -1).to(torch.int8).contiguous(), pi.to(dev).reshape(n, -1).to(torch.float32).contiguous(),
+            z.to(dev).reshape(n, -1).to(torch.float32).contiguous(), (valids.to(dev).reshape(n, -1) != 0).view(torch.uint8).contiguous(),
+            q.to(dev).reshape(n, -1).to(torch.float32).contiguous())
+    steps_per_epoch = n // batch_size
+    if steps_per_epoch == 0:
+        raise ValueError('fewer examples (%d) than batch_size (%d)' % (n, batch_size))
+    if batch_ids is not None:
+        ids_all = _check_batch_ids(batch_ids, epochs * steps_per_epoch, batch_size)
+        if ids_all.numel() and (int(ids_all.min()) < 0 or int(ids_all.max()) >= n):
+            raise ValueError('batch_ids holds an id outside [0, %d)' % n)
+        ids_all = ids_all.to(torch.int32).to(dev)
+    else:
+        rng_seed = int.from_bytes(os.urandom(8), 'little') if seed is None else int(seed)
+    module.to(dev).train()
+    opt = torch.optim.AdamW(module.parameters(), lr=learn_rate)
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=learn_rate, steps_per_epoch=steps_per_epoch, epochs=epochs)
+    hist = []
+    with torch.cuda.device(dev):
+        for ep in range(epochs):
+            if batch_ids is not None:
+                ids_ep = ids_all[ep * steps_per_epoch:(ep + 1) * steps_per_epoch]
+            else:
+                ids_ep = sample_ids(n, batch_size, steps_per_epoch, rng_seed, ep * steps_per_epoch, device=dev)
+            losses = torch.empty((steps_per_epoch, 2), dtype=torch.float64, device=dev)
+            for i_batch in range(steps_per_epoch):
+                b_boards, b_pi, b_z, b_valids, b_q = gather_batch(cols, ids_ep[i_batch])
+                if board_shape is not None:
+                    b_boards = b_boards.reshape((batch_size,) + tuple(board_shape)).to(torch.float32)
+                opt.zero_grad(set_to_none=True)
+                out_pi, out_v = module(b_boards, b_valids.view(torch.bool))
+                fused_loss(out_pi, out_v, b_pi, b_z, b_q, q_weight, 0.25, out=losses[i_batch]).backward()
+                opt.step()
+                sched.step()
+                if on_step is not None:
+                    on_step(ep, i_batch, i_batch + steps_per_epoch * ep)
+            got = losses.cpu().numpy()                                       # the epoch's one read
+            hist.extend((float(a), float(b)) for a, b in got)
+            if log:
+                log('epoch %d: pi loss %.4f  v loss %.4f' % (ep + 1, got[:, 0].mean(), got[:, 1].mean()))
     module.eval()
     return hist

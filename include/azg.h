@@ -161,6 +161,41 @@ int azg_eval_losses(const float* pi_dev, const float* v_dev, const float* target
                     const uint8_t* active_dev, int B, int A, int P, float q_weight, double* rows_dev, int32_t* flags_dev,
                     double* totals_dev, int accumulate, void* stream);
 
+/* ---- the training step's batches (GenericNNetWrapper.train :44-92) without the host: draw, gather, score ------------------------
+   Three calls that replace np.random.choice (:57), the five fancy-index reads (:58-63) and loss_pi / loss_v (:179-190) with their
+   backward pass down to the net's outputs.  Each enqueues on `stream` and returns; nothing is allocated, nothing is read back. */
+/* np.random.choice(n, batch, replace=False) for n_steps steps in ONE launch (one wave per step): ids_out_dev int32[n_steps][batch].
+   Row s is a function of (rng_seed, stream0 + s, n, batch) alone, on the RNG contract above, with exactly `batch` uniforms and no
+   rejection -- a Fisher-Yates shuffle over a virtual identity:
+       p = identity on [0, n);   for i = 0 .. batch - 1:   m = n - i,   j = i + min(floor(u01(rng_seed, stream0 + s, counter i) * m), m - 1),
+                                                           ids[i] = p[j],   p[j] = p[i]
+   (the product in f64).  Every ordered tuple of distinct indices is equally likely.  1 <= batch <= 8192, batch <= n < 2^31 and
+   n_steps >= 0 are required, anything else is an error and launches nothing; n_steps == 0 launches nothing and needs no pointer. */
+int azg_train_sample_ids(int64_t n, int batch, int n_steps, uint64_t rng_seed, uint64_t stream0, int32_t* ids_out_dev, void* stream);
+/* Rows ids_dev[0 .. B) of the five example columns in one launch (one wave per row): boards_dev int8[n][S], pi_dev f32[n][A], z_dev /
+   q_dev f32[n][P], valids_dev u8[n][A] -> out_boards_dev int8[B][S], out_pi_dev f32[B][A], out_z_dev / out_q_dev f32[B][P], out_valids_dev
+   u8[B][A] holding valids != 0 as 0 / 1 bytes (a bool tensor's storage).  Rows may start at any byte offset (S = 75, A = 21).  An id
+   outside [0, n) cannot be refused without reading the ids back: the row's content is then undefined (no memory outside the columns is
+   touched).  n < 1, B < 0, S < 1, A < 1, P outside 1 .. 8 or a NULL pointer (with B > 0) is an error and launches nothing. */
+int azg_train_gather(const int8_t* boards_dev, const float* pi_dev, const float* z_dev, const uint8_t* valids_dev, const float* q_dev,
+                     const int32_t* ids_dev, int n, int B, int S, int A, int P, int8_t* out_boards_dev, float* out_pi_dev, float* out_z_dev,
+                     uint8_t* out_valids_dev, float* out_q_dev, void* stream);
+/* loss_pi + loss_v (:179-190) of a training batch on the module's outputs -- log_pi_dev f32[B][A] are LOG-probabilities (masked actions
+   carry -1e8), v_dev f32[B][P] -- and the gradient of L = loss_pi + v_coeff * loss_v with respect to both.  Two launches: one wave per
+   row, then one wave for the totals.
+     rows_dev[b][0] = sum over the actions with t > 0 of t (log t - log_pi)   (t == 0 adds exactly 0 and gets the gradient 0, whatever
+                      log_pi holds);            rows_dev[b][1] = sum_p (t_v - v)^2,   t_v = (z + q_weight q) / (1 + q_weight)
+     out_dev[0] = sum_b rows[b][0] / B ('batchmean'),   out_dev[1] = sum_b rows[b][1] / (B P)
+   in f64 from the f32 inputs; lanes take entries in index order and are combined in one fixed tree, so the numbers are the same bits
+   in every call.  The gradients are f32, operation for operation what autograd computes on the GPU for the expression of train.train
+   (a tensor divided by a host scalar is multiplied by the scalar's f32 reciprocal there):
+     grad_log_pi_dev[b][a] = -(t (1 / B)),      grad_v_dev[b][p] = -((v_coeff (1 / (B P))) (2 (t_v - v))),   t_v = (z + q_weight q) (1 / (1 + q_weight))
+   with 1 + q_weight in f32.  When B and B P are powers of two every scale is exact.  B < 1, A < 1, P outside 1 .. 8, B or A above
+   2^31 - 65, q_weight <= -1 (or NaN) or a NULL pointer is an error and launches nothing. */
+int azg_train_losses(const float* log_pi_dev, const float* v_dev, const float* target_pi_dev, const float* z_dev, const float* q_dev,
+                     int B, int A, int P, float q_weight, float v_coeff, float* grad_log_pi_dev, float* grad_v_dev, double* rows_dev,
+                     double* out_dev, void* stream);
+
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */
 typedef struct azg_forest_cfg {

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Time one training step of train.train on the GPU, legacy path against device_batches=True, in one process.
+    python tools/time_train_step.py [--out profiles/r13_train_batches.md] [--sizes 65536,1048576] [--batch 512] [--warmup 50] [--steps 200]
+The Splendor-2p SplendorV80Module on n synthetic examples.  Per n and per path train.train itself runs warmup + steps optimiser steps
+(stopped from its on_step hook); the clock runs from a device synchronise after the warm-up to one after the last timed step, so the
+figure is wall time per step with everything a path makes the host do.  Separately: the kernel time of the three new launches by device
+events (sample_ids for one epoch of n // batch steps; gather and losses for one batch), and the CPU time of one torch.randperm(n), which
+the legacy path pays per step.  Prints a markdown report (and writes it to --out)."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+class _Stop(Exception):
+    pass
+
+
+def synthetic(n, device, seed=0):
+    """five columns on the device: int8 boards [n, 392], normalised pi on random valid sets [n, 81], z = +-1 per seat, valids u8, q"""
+    import torch
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    boards = torch.randint(0, 8, (n, 392), generator=g, device=device, dtype=torch.int8)
+    valids = torch.rand((n, 81), generator=g, device=device) < 0.4
+    valids[:, 0] = True
+    pi = torch.rand((n, 81), generator=g, device=device) * valids
+    pi = pi / pi.sum(1, keepdim=True)
+    z = torch.where(torch.rand((n, 1), generator=g, device=device) < 0.5, 1.0, -1.0) * torch.tensor([[1.0, -1.0]], device=device)
+    q = 0.5 * z * torch.rand((n, 2), generator=g, device=device)
+    return boards, pi.float(), z.float(), valids.to(torch.uint8), q.float()
+
+
+def time_path(ex, batch, warmup, steps, device_batches):
+    import torch
+    from azg_amd import train
+    n = ex[0].shape[0]
+    spe = n // batch
+    epochs = -(-(warmup + steps) // spe)
+    mark = {}
+
+    def on_step(ep, i_batch, step):
+        if step + 1 == warmup:
+            torch.cuda.synchronize()
+            mark['t0'] = time.perf_counter()
+        elif step + 1 == warmup + steps:
+            torch.cuda.synchronize()
+            mark['t1'] = time.perf_counter()
+            raise _Stop
+
+    torch.manual_seed(0)
+    m = train.SplendorV80Module(num_players=2, dropout=0.0)
+    try:
+        train.train(m, ex, learn_rate=3e-4, batch_size=batch, epochs=epochs, q_weight=0.5, device='cuda:0', seed=1, on_step=on_step,
+                    device_batches=device_batches)
+    except _Stop:
+        pass
+    return (mark['t1'] - mark['t0']) / steps * 1e3
+
+
+def event_ms(fn, reps=200, warm=20):
+    import torch
+    for _ in range(warm):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(reps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--sizes', default='65536,1048576')
+    ap.add_argument('--batch', type=int, default=512)
+    ap.add_argument('--warmup', type=int, default=50)
+    ap.add_argument('--steps', type=int, default=200)
+    ap.add_argument('--repeats', type=int, default=2, help='alternating runs of the two paths per size')
+    args = ap.parse_args(argv)
+    import torch
+    from azg_amd import train
+    if not torch.cuda.is_available():
+        raise SystemExit('time_train_step: needs a GPU (a CPU timing says nothing about it)')
+    dev = 'cuda:0'
+    lines = ['# Training step: legacy batches vs `device_batches=True` (`tools/time_train_step.py`)', '',
+             '%s, torch %s.  SplendorV80Module (2 players), batch %d, %d warm-up + %d timed optimiser steps per run, both paths in one process,'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.batch, args.warmup, args.steps),
+             'alternating; wall time between two device synchronisations / steps.  The legacy path is `train.train` with its defaults.', '',
+             '| n examples | legacy step (ms), per run | device step (ms), per run | device / legacy (best of each) | one `torch.randperm(n)` on the CPU (ms) |',
+             '|---|---|---|---|---|']
+    kern = ['', '## Kernel time of the new launches (device events, mean of 200 calls; 50 for the draw)', '',
+            '| n examples | `azg_train_sample_ids`, one epoch = n // batch steps (µs) | per step of that epoch (µs) | `azg_train_gather`, one batch (µs) | `azg_train_losses`, both launches (µs) |',
+            '|---|---|---|---|---|']
+    for n in [int(x) for x in args.sizes.split(',')]:
+        ex = synthetic(n, dev)
+        legacy, device = [], []
+        for _ in range(args.repeats):
+            legacy.append(time_path(ex, args.batch, args.warmup, args.steps, False))
+            device.append(time_path(ex, args.batch, args.warmup, args.steps, True))
+        g = torch.Generator(device='cpu')
+        g.manual_seed(1)
+        torch.randperm(n, generator=g)
+        t0 = time.perf_counter()
+        for _ in range(10):
+            torch.randperm(n, generator=g)
+        perm_ms = (time.perf_counter() - t0) / 10 * 1e3
+        fmt = lambda xs: ' / '.join('%.3f' % x for x in xs)  # noqa: E731
+        lines.append('| %d | %s | %s | %.3f | %.3f |' % (n, fmt(legacy), fmt(device), min(device) / min(legacy), perm_ms))
+        # the three launches on their own
+        spe = n // args.batch
+        ids = torch.empty((spe, args.batch), dtype=torch.int32, device=dev)
+        t_ids = event_ms(lambda: train.sample_ids(n, args.batch, spe, 1, 0, out=ids), reps=50, warm=5)
+        cols = tuple(x.contiguous() for x in (ex[0], ex[1], ex[2], ex[3], ex[4]))
+        outs = train.gather_batch(cols, ids[0])
+        t_gather = event_ms(lambda: train.gather_batch(cols, ids[0], out=outs))
+        lp = torch.log_softmax(torch.randn((args.batch, 81), device=dev), 1)
+        v = torch.tanh(torch.randn((args.batch, 2), device=dev))
+        out2 = torch.empty(2, dtype=torch.float64, device=dev)
+        t_loss = event_ms(lambda: train.train_losses(lp, v, outs[1], outs[2], outs[4], 0.5, out=out2))
+        kern.append('| %d | %.1f | %.3f | %.1f | %.1f |' % (n, t_ids * 1e3, t_ids * 1e3 / spe, t_gather * 1e3, t_loss * 1e3))
+        del ex, cols, outs
+        torch.cuda.empty_cache()
+    kern += ['', '(The device path draws an epoch\'s ids with one launch before the epoch\'s first step: where an epoch is longer than the warm-up',
+             'that launch is outside the timed window, and its share of a step is the third column.)',
+             '', '(The event figures include the Python wrapper\'s argument checks and, for the losses, its three buffer allocations between the',
+             'launches: they are the cost of the call as the trainer makes it, an upper bound of the kernels\' own time.)']
+    text = '\n'.join(lines + kern) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

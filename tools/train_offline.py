@@ -7,7 +7,8 @@ or try another nn_version, on a stored `checkpoint.examples` without playing a g
 With --training: the example history is flattened, the last tenth is held out as the test set unless --test names a file, the last
 nb_samples * 1000 of the rest are trained on with the test set validated every 1e5 // batch_size - 1 steps (NNetWrapper.train: the forward
 of the validation on the engine's one-launch kernel, the losses by azg_eval_losses), intermediary_<i>.pt and at the end last.pt are written
-into <output><last six digits of the time>/.  Same flags and defaults as the reference; no FLOP count is printed (that needs fvcore)."""
+into <output><last six digits of the time>/.  Same flags and defaults as the reference; no FLOP count is printed (that needs fvcore).
+--device-batches (not in the reference): the training batches are drawn, gathered and scored on the GPU, nothing is read back per step."""
 import argparse
 import os
 import sys
@@ -40,6 +41,12 @@ def build_parser():
     return parser
 
 
+def add_engine_options(parser):
+    """options of the engine's trainer that are no flag of the reference's (build_parser keeps to those)"""
+    parser.add_argument('--device-batches', action='store_true', help='Draw, gather and score the training batches on the GPU (train.train(device_batches=True)): no host synchronisation per step')
+    return parser
+
+
 def make_game(args):
     from azg_amd import games
     kw = {}
@@ -65,7 +72,7 @@ def flatten(path):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = add_engine_options(build_parser()).parse_args(argv)
     sys.path.insert(0, ROOT)
     import torch
     from azg_amd.nnet_wrapper import NNetWrapper
@@ -73,7 +80,7 @@ def main(argv=None):
     output = (args.output if args.output else 'output_') + str(int(time.time()))[-6:]
     g = make_game(args)
     nn_args = dict(lr=args.learn_rate, dropout=args.dropout, epochs=args.epochs, batch_size=args.batch_size, nn_version=args.nn_version,
-                   learn_rate=args.learn_rate, no_compression=False, q_weight=args.q_weight)
+                   learn_rate=args.learn_rate, no_compression=False, q_weight=args.q_weight, device_batches=args.device_batches)
     nnet = NNetWrapper(g, nn_args)
     if args.input:
         nnet.load_checkpoint(os.path.dirname(args.input), os.path.basename(args.input))
