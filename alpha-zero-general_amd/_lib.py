@@ -43,6 +43,7 @@ EXPORTS = [
     'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
     'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62', 'azg_pick_actions', 'azg_env_playouts',
     'azg_eval_losses', 'azg_train_sample_ids', 'azg_train_gather', 'azg_train_losses',
+    'azg_train_adamw', 'azg_train_step_advance',
 ]
 
 
@@ -119,6 +120,9 @@ def lib():
         L.azg_train_sample_ids.argtypes = [C.c_int64, i, i, u64, u64, vp, vp]
         L.azg_train_gather.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp]
         L.azg_train_losses.argtypes = [vp, vp, vp, vp, vp, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    if hasattr(L, 'azg_train_adamw'):                       # (absent from older builds loaded through AZG_LIB for A/B runs)
+        L.azg_train_adamw.argtypes = [vp, i, vp, i, vp, i, vp, vp]
+        L.azg_train_step_advance.argtypes = [vp, vp]
     if hasattr(L, 'azg_debug_rng_u01'):                     # (test aid, include/azg_testaids.h)
         L.azg_debug_rng_u01.argtypes = [u64, u64, u64, i, i, vp, vp]
     L.azg_stream_create_xcd.argtypes = [i, i, C.POINTER(vp)]

@@ -1,5 +1,5 @@
 // azg_train.hip -- the training step's batch kernels (train.hip.h) and their C-ABI: azg_train_sample_ids, azg_train_gather,
-// azg_train_losses.  A translation unit of its own, like azg_loss.hip: nothing here can change what the compiler makes of a kernel that
+// azg_train_losses; the optimiser's: azg_train_adamw, azg_train_step_advance.  A translation unit of its own, like azg_loss.hip: nothing here can change what the compiler makes of a kernel that
 // was there before.
 #include <hip/hip_runtime.h>
 #include <string>
@@ -51,6 +51,27 @@ extern "C" int azg_train_losses(const float* log_pi, const float* v, const float
     k_train_loss_rows<<<dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream>>>(log_pi, v, target_pi, z, q, B, A, P, q_weight, inv_1q, inv_b, g_v,
                                                                              grad_log_pi, grad_v, rows);
     k_train_loss_totals<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>(rows, B, P, out);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+static_assert(sizeof(TrainAdamwSeg) == sizeof(azg_adamw_seg) && sizeof(TrainAdamwChunk) == sizeof(azg_adamw_chunk), "include/azg.h and train.hip.h disagree");
+
+extern "C" int azg_train_adamw(const azg_adamw_seg* segs, int n_segs, const azg_adamw_chunk* chunks, int n_chunks, const float* table,
+                               int total_steps, const int64_t* step, void* stream) {
+    if (!segs || !chunks || !table || !step) return fail("azg_train_adamw: a required pointer is NULL");
+    if (n_segs < 1) return fail("azg_train_adamw: n_segs >= 1 is required");
+    if (n_chunks < 1) return fail("azg_train_adamw: n_chunks >= 1 is required");
+    if (total_steps < 1) return fail("azg_train_adamw: total_steps >= 1 is required");
+    k_adamw_onecycle<<<dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream>>>((const TrainAdamwSeg*)segs, n_segs, (const TrainAdamwChunk*)chunks,
+                                                                                   table, total_steps, (const long long*)step);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int azg_train_step_advance(int64_t* step, void* stream) {
+    if (!step) return fail("azg_train_step_advance: step is NULL");
+    k_adamw_step_advance<<<dim3(1), dim3(64), 0, (hipStream_t)stream>>>((long long*)step);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -7,6 +7,8 @@
 // k_train_loss_rows / k_train_loss_totals: one wave per row / ONE wave for the totals, as loss.hip.h -- sums in f64, lanes in index order
 //   and one fixed xor tree, so the numbers are the same bits in every call; the gradients in f32, operation for operation what autograd
 //   computes for train.loss_pi + v_coeff * train.loss_v.
+// k_adamw_onecycle / k_adamw_step_advance: the optimiser step of :81-82 (AdamW + OneCycleLR) for ALL parameters in one launch, with the
+//   step's scalars taken from a table row that a counter in device memory picks; then the counter's increment.  No atomics, no LDS.
 #pragma once
 #include "azg_common.hip.h"
 
@@ -164,6 +166,91 @@ __global__ __launch_bounds__(64) void k_train_loss_totals(const double* __restri
     s1 = train_wave_tree_sum_f64(s1);
     if (l == 0) out[0] = s0 / (double)B;
     if (l == 1) out[1] = s1 / ((double)B * (double)P);
+}
+
+// ---- the optimiser: torch.optim.AdamW under OneCycleLR in ONE launch, the step number read from device memory ---------------------------
+// (the two kernels below are named k_adamw_*, not k_train_*: tests/test_train_batches_surface.py counts the k_train_ kernels of this unit)
+constexpr int TRAIN_ADAMW_CHUNK = 2048;                    // elements per workgroup: 256 lanes x two float4
+struct TrainAdamwSeg { float* p; const float* g; float* m; float* v; long long numel; };     // azg_adamw_seg of include/azg.h
+struct TrainAdamwChunk { int seg, first; };                                                 // azg_adamw_chunk
+
+// one element of torch's foreach AdamW (_multi_tensor_adamw, not capturable, no amsgrad), every operation rounded on its own:
+//   p *= r0;  m += r1 (g - m);  v *= r2;  v += (g g) r3;  p -= r4 (m / (sqrt(v) / r5 + r6))
+__device__ __forceinline__ void train_adamw_elem(float& p, float g, float& m, float& v, float r0, float r1, float r2, float r3, float r4,
+                                                 float r5, float r6) {
+    p = __fmul_rn(p, r0);
+    m = __fadd_rn(m, __fmul_rn(r1, __fsub_rn(g, m)));
+    v = __fmul_rn(v, r2);
+    v = __fadd_rn(v, __fmul_rn(__fmul_rn(g, g), r3));
+    const float d = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), r5), r6);
+    p = __fsub_rn(p, __fmul_rn(r4, __fdiv_rn(m, d)));
+}
+
+// workgroup c updates elements [first, first + 2048) (or up to numel) of segment chunks[c].seg with row clamp(*step, 0, total_steps - 1) of
+// the table.  Everything but the elements is wave-uniform: the step, the table row, the chunk and its segment arrive in scalar registers.
+// 16-byte accesses when the chunk is whole and the segment's four pointers are 16-byte aligned (`first` is a multiple of 2048), else one
+// element per lane and trip.  A chunk that names no segment, or starts outside its segment, touches nothing.
+__global__ __launch_bounds__(256) void k_adamw_onecycle(const TrainAdamwSeg* __restrict__ segs, int n_segs,
+                                                        const TrainAdamwChunk* __restrict__ chunks, const float* __restrict__ table,
+                                                        int total_steps, const long long* __restrict__ step) {
+    long long s = *step;
+    s = s < 0 ? 0 : (s > (long long)total_steps - 1 ? (long long)total_steps - 1 : s);
+    const float* r = table + 8 * s;
+    const float r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5], r6 = r[6];
+    const TrainAdamwChunk c = chunks[blockIdx.x];
+    if ((unsigned)c.seg >= (unsigned)n_segs) return;
+    const TrainAdamwSeg sg = segs[c.seg];
+    if (c.first < 0 || (long long)c.first >= sg.numel) return;
+    const long long left = sg.numel - (long long)c.first;
+    // (the pointers come out of a table: without the address space the compiler can only use flat accesses)
+    typedef __attribute__((address_space(1))) float gf32;
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(1))) f32x4 gf32x4;
+    gf32* p = (gf32*)sg.p + c.first;
+    const gf32* g = (const gf32*)sg.g + c.first;
+    gf32* m = (gf32*)sg.m + c.first;
+    gf32* v = (gf32*)sg.v + c.first;
+    const bool aligned = ((((uintptr_t)sg.p) | ((uintptr_t)sg.g) | ((uintptr_t)sg.m) | ((uintptr_t)sg.v)) & 15) == 0 && (c.first & 3) == 0;
+    if (aligned && left >= TRAIN_ADAMW_CHUNK) {
+        f32x4 p4[2], g4[2], m4[2], v4[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {                                   // all eight loads first: the kernel is bound by memory
+            const int i = (int)threadIdx.x + 256 * k;
+            p4[k] = ((const gf32x4*)p)[i];
+            g4[k] = ((const gf32x4*)g)[i];
+            m4[k] = ((const gf32x4*)m)[i];
+            v4[k] = ((const gf32x4*)v)[i];
+        }
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int i = (int)threadIdx.x + 256 * k;
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                float pe = p4[k][e], me = m4[k][e], ve = v4[k][e];
+                train_adamw_elem(pe, g4[k][e], me, ve, r0, r1, r2, r3, r4, r5, r6);
+                p4[k][e] = pe;
+                m4[k][e] = me;
+                v4[k][e] = ve;
+            }
+            ((gf32x4*)p)[i] = p4[k];
+            ((gf32x4*)m)[i] = m4[k];
+            ((gf32x4*)v)[i] = v4[k];
+        }
+    } else {
+        const int cnt = left < TRAIN_ADAMW_CHUNK ? (int)left : TRAIN_ADAMW_CHUNK;
+        for (int i = (int)threadIdx.x; i < cnt; i += 256) {
+            float pi = p[i], mi = m[i], vi = v[i];
+            train_adamw_elem(pi, g[i], mi, vi, r0, r1, r2, r3, r4, r5, r6);
+            p[i] = pi;
+            m[i] = mi;
+            v[i] = vi;
+        }
+    }
+}
+
+// *step += 1 -- a launch of its own behind k_adamw_onecycle on the same stream: no workgroup of the update can see the new value
+__global__ __launch_bounds__(64) void k_adamw_step_advance(long long* __restrict__ step) {
+    if (threadIdx.x == 0) *step = *step + 1;
 }
 
 }  // namespace azg

@@ -148,7 +148,9 @@ class NNetWrapper:
         """With a validation_set: every `every` steps (when (i_batch + steps_per_epoch * epoch) % every == 0, :86) the set is evaluated
         with the weights and BatchNorm statistics of that moment, the loss goes to `log` (print when None) and into
         self.validation_history as (step, loss), and where i_batch > 0 and save_folder is given intermediary_<i_batch>.pt is saved (:89-90).
-        nn_args['device_batches'] (default False): draw, gather and score the batches on the GPU (train.train(device_batches=True))"""
+        nn_args['device_batches'] (default False): draw, gather and score the batches on the GPU (train.train(device_batches=True))
+        nn_args['device_optimizer'] / nn_args['graph_step'] (default False): the one-launch AdamW + OneCycleLR, and a step as one graph
+        replay (train.train(device_optimizer=True) / (graph_step=True)); both need device_batches"""
         cols = self._cols(examples)
         on_step = None
         self.validation_history = []
@@ -173,7 +175,8 @@ class NNetWrapper:
         hist = _train.train(self.nnet, cols, learn_rate=float(lr), batch_size=int(self._arg('batch_size', 32)),
                             epochs=int(self._arg('epochs', 1)), q_weight=float(self._arg('q_weight', 0.5)),
                             device=str(self.game.device), seed=seed, log=log, board_shape=self.board_size if self._custom else None,
-                            on_step=on_step, device_batches=bool(self._arg('device_batches', False)))
+                            on_step=on_step, device_batches=bool(self._arg('device_batches', False)),
+                            device_optimizer=bool(self._arg('device_optimizer', False)), graph_step=bool(self._arg('graph_step', False)))
         self._eval = None
         return hist
 

@@ -565,8 +565,147 @@ def fused_loss(log_pi, v, target_pi, z, q, q_weight, v_coeff=0.25, out=None):
     return _FusedLoss.apply(log_pi, v, target_pi, z, q, q_weight, v_coeff, out)
 
 
+def onecycle_adamw_table(max_lr, total_steps, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    """-> numpy f32[total_steps, 8]: row s holds the scalars torch.optim.AdamW uses in optimiser step s (0-based) when
+    OneCycleLR(opt, max_lr=max_lr, total_steps=total_steps) has been stepped s times after construction (the table of azg_train_adamw,
+    include/azg.h):  { 1 - lr wd, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1^k), (1 - beta2^k)^0.5, eps, 0 },  k = s + 1.
+    lr and beta1 (OneCycleLR cycles the momentum, 0.95 -> 0.85 -> 0.95) are read from torch's own scheduler, run here once on a dummy
+    one-parameter AdamW; the rest is derived in Python floats exactly as torch's _multi_tensor_adamw does (the bias correction with the
+    CURRENT beta1), and every value is cast to f32 once."""
+    total_steps = int(total_steps)
+    if total_steps < 1:
+        raise ValueError('onecycle_adamw_table: total_steps >= 1 is required, got %d' % total_steps)
+    opt = torch.optim.AdamW([nn.Parameter(torch.zeros(1))], lr=max_lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=max_lr, total_steps=total_steps)
+    table = np.zeros((total_steps, 8), dtype=np.float32)
+    for s in range(total_steps):
+        group = opt.param_groups[0]
+        lr, (beta1, beta2), k = float(group['lr']), (float(b) for b in group['betas']), float(s + 1)
+        table[s] = [1 - lr * weight_decay, 1 - beta1, beta2, 1 - beta2, lr / (1 - beta1 ** k), (1 - beta2 ** k) ** 0.5, eps, 0.0]
+        if s + 1 < total_steps:
+            opt.step()                                                       # (no gradient: a no-op that keeps the scheduler's call order)
+            sched.step()
+    return table
+
+
+ADAMW_CHUNK = 2048                                                           # csrc/train.hip.h TRAIN_ADAMW_CHUNK
+
+
+def adamw_tables(quads):
+    """The segment and chunk tables of azg_train_adamw for quads = [(p, g, m, v), ...], contiguous f32 CUDA tensors of one numel per
+    quadruple (any alignment, any offset into their storage) -> (segs int64[n, 5], chunks int32[n_chunks, 2]) on the tensors' device.
+    The tables hold the tensors' addresses: they are good for as long as the tensors are."""
+    segs, chunks, dev = [], [], None
+    for k, quad in enumerate(quads):
+        n = quad[0].numel()
+        dev = quad[0].device if dev is None else dev
+        for t in quad:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n and t.device == dev):
+                raise ValueError('adamw_tables: p, g, m and v of a segment must be contiguous f32 CUDA tensors of one size on one device')
+        if n >= 2 ** 31:
+            raise ValueError('adamw_tables: a segment must hold fewer than 2^31 elements')
+        segs.append([t.data_ptr() for t in quad] + [n])
+        chunks.extend((k, first) for first in range(0, n, ADAMW_CHUNK))
+    if not chunks:
+        raise ValueError('adamw_tables: no element to update')
+    return (torch.tensor(segs, dtype=torch.int64).to(dev), torch.tensor(chunks, dtype=torch.int32).to(dev))
+
+
+def adamw_update(segs, chunks, table, step):
+    """azg_train_adamw: one launch on the current stream updates every segment of adamw_tables() with row clamp(step[0], 0, len(table) - 1)
+    of table (f32[total_steps, 8], CUDA); step is an int64[1] CUDA tensor that the launch only reads.  Nothing is synchronised."""
+    from . import _lib
+    assert segs.is_cuda and segs.dtype == torch.int64 and segs.dim() == 2 and segs.shape[1] == 5 and segs.is_contiguous(), 'adamw_update: segs'
+    assert chunks.dtype == torch.int32 and chunks.dim() == 2 and chunks.shape[1] == 2 and chunks.is_contiguous(), 'adamw_update: chunks'
+    assert table.dtype == torch.float32 and table.dim() == 2 and table.shape[1] == 8 and table.is_contiguous(), 'adamw_update: table'
+    assert step.dtype == torch.int64 and step.numel() == 1, 'adamw_update: step'
+    assert chunks.device == segs.device and table.device == segs.device and step.device == segs.device, 'adamw_update: one device'
+    with torch.cuda.device(segs.device):
+        _lib.check(_lib.lib().azg_train_adamw(_ptr(segs), segs.shape[0], _ptr(chunks), chunks.shape[0], _ptr(table), table.shape[0], _ptr(step),
+                                              _stream()))
+
+
+def adamw_step_advance(step):
+    """azg_train_step_advance: step[0] += 1 (int64[1], CUDA) in a launch of its own on the current stream"""
+    from . import _lib
+    assert step.is_cuda and step.dtype == torch.int64 and step.numel() == 1, 'adamw_step_advance: step must be an int64[1] CUDA tensor'
+    with torch.cuda.device(step.device):
+        _lib.check(_lib.lib().azg_train_step_advance(_ptr(step), _stream()))
+
+
+class DeviceAdamW:
+    """torch.optim.AdamW(params, lr=max_lr, betas, eps, weight_decay) under OneCycleLR(max_lr=max_lr, total_steps=total_steps) with no
+    per-step value on the host: step() is azg_train_adamw + azg_train_step_advance (csrc/train.hip.h) on the current stream, the step number
+    lives in device memory (step_counter, never read back) and picks a row of onecycle_adamw_table.  No amsgrad, no maximize.
+    It owns one flat f32 buffer each for the moments m and v (zeroed) and one for the gradients; a parameter's segment starts at a multiple
+    of 4 floats.  The parameters must be contiguous f32 CUDA tensors that stay where they are (call module.to(device) first).
+    The FIRST backward runs with every .grad unset: step() then knows which parameters received a gradient -- one that requires grad and
+    got none raises ValueError (torch would skip it; one launch over fixed tables cannot) -- moves the gradients into the flat buffer and
+    makes every .grad a view of it.  From then on zero_grad() is one memset and backward accumulates into the views (0 + g is g)."""
+
+    def __init__(self, params, max_lr, total_steps, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        self.params = [p for p in params if p.requires_grad and p.numel() > 0]
+        if not self.params:
+            raise ValueError('DeviceAdamW: no parameter to optimise')
+        dev = self.params[0].device
+        for p in self.params:
+            if not (p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.is_contiguous()):
+                raise ValueError('DeviceAdamW: the parameters must be contiguous f32 CUDA tensors on one device')
+        self.total_steps = int(total_steps)
+        self.offsets, total = [], 0
+        for p in self.params:
+            self.offsets.append(total)
+            total += -(-p.numel() // 4) * 4
+        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.table = torch.from_numpy(onecycle_adamw_table(max_lr, self.total_steps, betas, eps, weight_decay)).to(dev)
+        self.step_counter = torch.zeros(1, dtype=torch.int64, device=dev)
+        cut = lambda flat: [flat[o:o + p.numel()] for o, p in zip(self.offsets, self.params)]  # noqa: E731
+        self.grad_views = [g.view_as(p) for g, p in zip(cut(self.flat_grad), self.params)]
+        self.segs, self.chunks = adamw_tables(list(zip([p.detach() for p in self.params], cut(self.flat_grad), cut(self.exp_avg),
+                                                       cut(self.exp_avg_sq))))
+        self.steps_taken = 0                                                   # the host's count: the device counter is never read back
+        self._adopted = False
+        for p in self.params:
+            p.grad = None
+
+    def zero_grad(self):
+        if self._adopted:
+            self.flat_grad.zero_()
+
+    def _check_limit(self):
+        if self.steps_taken >= self.total_steps:
+            raise ValueError('DeviceAdamW: tried to step %d times, the schedule has total_steps = %d' % (self.steps_taken + 1, self.total_steps))
+
+    def count_step(self):
+        """the host's count of one step; raises before a (total_steps + 1)-th, where OneCycleLR raises"""
+        self._check_limit()
+        self.steps_taken += 1
+
+    def launch(self):
+        """the two launches of a step without the host's count -- what a graph captures (count_step() then goes with each replay)"""
+        if not self._adopted:
+            missing = [k for k, p in enumerate(self.params) if p.grad is None]
+            if missing:
+                raise ValueError('DeviceAdamW: %d of %d parameters that require grad received none in the first backward (the first is '
+                                 'number %d, shape %s): freeze it (requires_grad=False) or leave it out' %
+                                 (len(missing), len(self.params), missing[0], tuple(self.params[missing[0]].shape)))
+            torch._foreach_copy_(self.grad_views, [p.grad for p in self.params])
+            for p, g in zip(self.params, self.grad_views):
+                p.grad = g
+            self._adopted = True
+        adamw_update(self.segs, self.chunks, self.table, self.step_counter)
+        adamw_step_advance(self.step_counter)
+
+    def step(self):
+        self._check_limit()
+        self.launch()
+        self.steps_taken += 1
+
+
 def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=0.5, device='cuda:0', seed=None, log=None, board_shape=None,
-          device_batches=False, batch_ids=None, on_step=None):
+          device_batches=False, batch_ids=None, device_optimizer=False, graph_step=False, info=None, on_step=None):
     """examples = (boards int8[n,S], pi f32[n,A], z f32[n,P], valids u8/bool[n,A], q f32[n,P]) tensors or arrays.
     board_shape: give it for a module that expects the reference's inputs (float boards of getBoardSize(), bool valids:
     GenericNNetWrapper.py:60-63) instead of the engine modules' flat int8 boards.
@@ -575,9 +714,26 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
     batch_ids: an int array [epochs * steps_per_epoch, batch_size]: row `step` is that step's batch instead of a draw (either path; the
     generator is then not used).
     device_batches=True (CUDA only): the batches never touch the host -- _train_device_batches.  With the defaults nothing changes.
+    device_optimizer=True (needs device_batches=True and a CUDA device): DeviceAdamW in place of torch's AdamW + OneCycleLR -- the update of
+    all parameters and the schedule in one launch (azg_train_adamw), the step number in device memory.  Still eager, the same call order.
+    graph_step=True (implies device_optimizer=True): step 0 runs eagerly on a side stream -- the warm-up that a capture needs, and a real
+    training step --, then ONE step (row pick, gather, forward, loss, backward, optimiser) is captured with torch.cuda.graph and every later
+    step is one replay.  on_step is still called from the host after every step, on weights that are updated in place.  A module that cannot
+    be captured raises: there is no fallback.  With a single step in all nothing is captured.  Under capture dropout draws from torch's
+    graph-safe Philox state: with dropout > 0 its random stream differs from the eager paths'.
+    info: a dict that receives {'optimizer': 'torch' | 'device', 'graph_replays': int}.
     Returns the list of (pi loss, v loss) per step."""
+    device_optimizer = bool(device_optimizer) or bool(graph_step)
+    if device_optimizer and torch.device(device).type != 'cuda':
+        raise ValueError('train: device_optimizer=True%s needs a CUDA device, got %r (there is no CPU form of the optimiser kernel)'
+                         % (' (implied by graph_step=True)' if graph_step else '', device))
+    if device_optimizer and not device_batches:
+        raise ValueError('train: device_optimizer=True%s needs device_batches=True' % (' (implied by graph_step=True)' if graph_step else ''))
+    if isinstance(info, dict):
+        info.update(optimizer='device' if device_optimizer else 'torch', graph_replays=0)
     if device_batches:
-        return _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids)
+        return _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids,
+                                     device_optimizer, bool(graph_step), info if isinstance(info, dict) else None)
     boards, pi, z, valids, q = [torch.as_tensor(np.asarray(x.cpu()) if hasattr(x, 'cpu') else x).to(device) for x in examples[:5]]
     n = boards.shape[0]
     valids = valids.bool()
@@ -627,11 +783,13 @@ def _check_batch_ids(batch_ids, steps, batch_size):
     return ids.long()
 
 
-def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids):
+def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids,
+                          device_optimizer=False, graph_step=False, info=None):
     """train() with the batches drawn, gathered and scored on the GPU (csrc/train.hip.h): the columns are made contiguous on the device once;
     one sample_ids launch draws an epoch's ids (rng_seed = seed, or fresh entropy when None; stream0 = epoch * steps_per_epoch); a step is
     gather_batch, the module's forward, fused_loss, backward, opt.step(), sched.step(); the losses land in a device buffer f64[steps, 2]
-    that is read once per epoch.  The host waits for the GPU at the end of an epoch only (and wherever on_step does)."""
+    that is read once per epoch.  The host waits for the GPU at the end of an epoch only (and wherever on_step does).
+    device_optimizer: DeviceAdamW is both opt and sched.  graph_step: _train_graph_steps runs the steps."""
     if torch.device(device).type != 'cuda':
         raise ValueError('train: device_batches=True needs a CUDA device, got %r (there is no CPU form of the batch kernels)' % (device,))
     dev = torch.device(device)
@@ -651,10 +809,19 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
     else:
         rng_seed = int.from_bytes(os.urandom(8), 'little') if seed is None else int(seed)
     module.to(dev).train()
-    opt = torch.optim.AdamW(module.parameters(), lr=learn_rate)
-    sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=learn_rate, steps_per_epoch=steps_per_epoch, epochs=epochs)
+    if device_optimizer:
+        opt, sched = DeviceAdamW(module.parameters(), learn_rate, epochs * steps_per_epoch), None
+    else:
+        opt = torch.optim.AdamW(module.parameters(), lr=learn_rate)
+        sched = torch.optim.lr_scheduler.OneCycleLR(opt, max_lr=learn_rate, steps_per_epoch=steps_per_epoch, epochs=epochs)
     hist = []
     with torch.cuda.device(dev):
+        if graph_step:
+            if batch_ids is None:                                            # every epoch's ids before the capture: row s of epoch e is
+                ids_all = sample_ids(n, batch_size, epochs * steps_per_epoch, rng_seed, 0, device=dev)   # stream e * steps_per_epoch + s
+            hist = _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info)
+            module.eval()
+            return hist
         for ep in range(epochs):
             if batch_ids is not None:
                 ids_ep = ids_all[ep * steps_per_epoch:(ep + 1) * steps_per_epoch]
@@ -665,11 +832,15 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
                 b_boards, b_pi, b_z, b_valids, b_q = gather_batch(cols, ids_ep[i_batch])
                 if board_shape is not None:
                     b_boards = b_boards.reshape((batch_size,) + tuple(board_shape)).to(torch.float32)
-                opt.zero_grad(set_to_none=True)
+                if sched is None:
+                    opt.zero_grad()
+                else:
+                    opt.zero_grad(set_to_none=True)
                 out_pi, out_v = module(b_boards, b_valids.view(torch.bool))
                 fused_loss(out_pi, out_v, b_pi, b_z, b_q, q_weight, 0.25, out=losses[i_batch]).backward()
                 opt.step()
-                sched.step()
+                if sched is not None:
+                    sched.step()
                 if on_step is not None:
                     on_step(ep, i_batch, i_batch + steps_per_epoch * ep)
             got = losses.cpu().numpy()                                       # the epoch's one read
@@ -677,4 +848,56 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
             if log:
                 log('epoch %d: pi loss %.4f  v loss %.4f' % (ep + 1, got[:, 0].mean(), got[:, 1].mean()))
     module.eval()
+    return hist
+
+
+def _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info):
+    """The steps of train(graph_step=True), the current device being the columns': ids_all int32[total_steps, batch] on the device, opt a
+    DeviceAdamW.  The step body reads no host value that changes: its row of ids_all and its row of the loss buffer are picked by a device
+    index made from opt.step_counter with torch ops, and the optimiser takes its scalars by the same counter.  Everything is enqueued on
+    one stream, so the captured graph is one linear chain."""
+    dev = cols[0].device
+    total = epochs * steps_per_epoch
+    losses = torch.zeros((total, 2), dtype=torch.float64, device=dev)
+    loss2 = torch.zeros(2, dtype=torch.float64, device=dev)
+    outs = tuple(torch.empty((batch_size, x.shape[1]), dtype=x.dtype, device=dev) for x in cols)
+
+    def body():
+        idx = opt.step_counter.clamp(0, total - 1)                           # int64[1]: this step's number
+        gather_batch(cols, ids_all.index_select(0, idx)[0], out=outs)
+        b_boards = outs[0]
+        if board_shape is not None:
+            b_boards = b_boards.reshape((batch_size,) + tuple(board_shape)).to(torch.float32)
+        opt.zero_grad()
+        out_pi, out_v = module(b_boards, outs[3].view(torch.bool))
+        loss = fused_loss(out_pi, out_v, outs[1], outs[2], outs[4], q_weight, 0.25, out=loss2)
+        losses.index_copy_(0, idx, loss2[None])
+        loss.backward()
+        opt.launch()
+
+    side = torch.cuda.Stream(device=dev)                                     # step 0, eagerly: the warm-up of torch's capture recipe
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        opt.count_step()
+        body()
+    torch.cuda.current_stream().wait_stream(side)
+    graph, hist = None, []
+    for ep in range(epochs):
+        for i_batch in range(steps_per_epoch):
+            step = i_batch + steps_per_epoch * ep
+            if step > 0:
+                if graph is None:
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph):
+                        body()
+                opt.count_step()
+                graph.replay()
+                if info is not None:
+                    info['graph_replays'] += 1
+            if on_step is not None:
+                on_step(ep, i_batch, step)
+        got = losses[ep * steps_per_epoch:(ep + 1) * steps_per_epoch].cpu().numpy()     # the epoch's one read
+        hist.extend((float(a), float(b)) for a, b in got)
+        if log:
+            log('epoch %d: pi loss %.4f  v loss %.4f' % (ep + 1, got[:, 0].mean(), got[:, 1].mean()))
     return hist

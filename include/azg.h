@@ -195,6 +195,24 @@ int azg_train_gather(const int8_t* boards_dev, const float* pi_dev, const float*
 int azg_train_losses(const float* log_pi_dev, const float* v_dev, const float* target_pi_dev, const float* z_dev, const float* q_dev,
                      int B, int A, int P, float q_weight, float v_coeff, float* grad_log_pi_dev, float* grad_v_dev, double* rows_dev,
                      double* out_dev, void* stream);
+/* torch.optim.AdamW under OneCycleLR (:49-51, :81-82) for every parameter in ONE launch, the step number taken
+   from device memory: nothing in the call changes from step to step, so a captured graph can replay it.
+     segs_dev[n_segs]: one entry per parameter tensor -- p (updated), g (its gradient), m / v (the two moments, updated), numel < 2^31;
+     chunks_dev[n_chunks]: { seg, first }: one workgroup of 256 lanes updates elements [first, min(first + 2048, numel)) of segment seg;
+                       first is a multiple of 2048.  A chunk that names no segment or starts outside it touches nothing;
+     table_dev f32[total_steps][8]: row s = { 1 - lr_s wd, 1 - beta1_s, beta2, 1 - beta2, lr_s / (1 - beta1_s^(s+1)), sqrt(1 - beta2^(s+1)),
+                       eps, 0 }, the scalars of optimiser step s computed on the host in f64 and cast once (train.onecycle_adamw_table);
+     step_dev: the counter; every workgroup reads it once and uses row clamp(*step_dev, 0, total_steps - 1).
+   Per element in f32, each operation rounded on its own (no contraction), in the order of torch's foreach AdamW, r = the row:
+     p = p r0;   m = m + r1 (g - m);   v = v r2;   v = v + (g g) r3;   d = sqrt(v) / r5 + r6;   p = p - r4 (m / d)
+   16-byte loads and stores where a chunk is whole and its segment's four pointers are 16-byte aligned, single floats otherwise.
+   A NULL pointer, n_segs < 1, n_chunks < 1 or total_steps < 1 is an error and launches nothing. */
+typedef struct azg_adamw_seg { float* p; const float* g; float* m; float* v; int64_t numel; } azg_adamw_seg;
+typedef struct azg_adamw_chunk { int32_t seg, first; } azg_adamw_chunk;
+int azg_train_adamw(const azg_adamw_seg* segs_dev, int n_segs, const azg_adamw_chunk* chunks_dev, int n_chunks, const float* table_dev,
+                    int total_steps, const int64_t* step_dev, void* stream);
+/* *step_dev += 1 in a one-wave launch of its own: enqueued behind azg_train_adamw, no workgroup of the update can see the new value. */
+int azg_train_step_advance(int64_t* step_dev, void* stream);
 
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */

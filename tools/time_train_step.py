@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Time one training step of train.train on the GPU, legacy path against device_batches=True, in one process.
-    python tools/time_train_step.py [--out profiles/r13_train_batches.md] [--sizes 65536,1048576] [--batch 512] [--warmup 50] [--steps 200]
+"""Time one training step of train.train on the GPU in one process: the legacy path, device_batches=True, the eager device optimiser
+(device_optimizer=True) and a step as one graph replay (graph_step=True).
+    python tools/time_train_step.py [--out profiles/r14_train_graph_step.md] [--sizes 65536,1048576] [--batch 512] [--warmup 50] [--steps 200]
 The Splendor-2p SplendorV80Module on n synthetic examples.  Per n and per path train.train itself runs warmup + steps optimiser steps
 (stopped from its on_step hook); the clock runs from a device synchronise after the warm-up to one after the last timed step, so the
-figure is wall time per step with everything a path makes the host do.  Separately: the kernel time of the three new launches by device
-events (sample_ids for one epoch of n // batch steps; gather and losses for one batch), and the CPU time of one torch.randperm(n), which
-the legacy path pays per step.  Prints a markdown report (and writes it to --out)."""
+figure is wall time per step with everything a path makes the host do.  The paths alternate, `--repeats` rounds per size.  Separately: the
+kernel time of the batch launches by device events (sample_ids for one epoch of n // batch steps; gather and losses for one batch), of the
+optimiser's two launches on the V80 parameter set against torch's AdamW step on the same set, and the CPU time of one torch.randperm(n),
+which the legacy path pays per step.  Prints a markdown report (and writes it to --out)."""
 import argparse
 import os
 import sys
@@ -34,7 +36,11 @@ def synthetic(n, device, seed=0):
     return boards, pi.float(), z.float(), valids.to(torch.uint8), q.float()
 
 
-def time_path(ex, batch, warmup, steps, device_batches):
+PATHS = (('legacy', dict()), ('device_batches', dict(device_batches=True)),
+         ('device_optimizer', dict(device_batches=True, device_optimizer=True)), ('graph_step', dict(device_batches=True, graph_step=True)))
+
+
+def time_path(ex, batch, warmup, steps, switches):
     import torch
     from azg_amd import train
     n = ex[0].shape[0]
@@ -55,7 +61,7 @@ def time_path(ex, batch, warmup, steps, device_batches):
     m = train.SplendorV80Module(num_players=2, dropout=0.0)
     try:
         train.train(m, ex, learn_rate=3e-4, batch_size=batch, epochs=epochs, q_weight=0.5, device='cuda:0', seed=1, on_step=on_step,
-                    device_batches=device_batches)
+                    **switches)
     except _Stop:
         pass
     return (mark['t1'] - mark['t0']) / steps * 1e3
@@ -82,28 +88,29 @@ def main(argv=None):
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--steps', type=int, default=200)
-    ap.add_argument('--repeats', type=int, default=2, help='alternating runs of the two paths per size')
+    ap.add_argument('--repeats', type=int, default=2, help='alternating rounds of the four paths per size')
     args = ap.parse_args(argv)
     import torch
     from azg_amd import train
     if not torch.cuda.is_available():
         raise SystemExit('time_train_step: needs a GPU (a CPU timing says nothing about it)')
     dev = 'cuda:0'
-    lines = ['# Training step: legacy batches vs `device_batches=True` (`tools/time_train_step.py`)', '',
-             '%s, torch %s.  SplendorV80Module (2 players), batch %d, %d warm-up + %d timed optimiser steps per run, both paths in one process,'
+    lines = ['# Training step: legacy, `device_batches`, `device_optimizer`, `graph_step` (`tools/time_train_step.py`)', '',
+             '%s, torch %s.  SplendorV80Module (2 players), batch %d, %d warm-up + %d timed optimiser steps per run, the four paths in one'
              % (torch.cuda.get_device_name(0), torch.__version__, args.batch, args.warmup, args.steps),
-             'alternating; wall time between two device synchronisations / steps.  The legacy path is `train.train` with its defaults.', '',
-             '| n examples | legacy step (ms), per run | device step (ms), per run | device / legacy (best of each) | one `torch.randperm(n)` on the CPU (ms) |',
-             '|---|---|---|---|---|']
-    kern = ['', '## Kernel time of the new launches (device events, mean of 200 calls; 50 for the draw)', '',
+             'process, alternating; wall time between two device synchronisations / steps.  The legacy path is `train.train` with its defaults;',
+             '`device_optimizer` and `graph_step` run with `device_batches=True`.', '',
+             '| n examples | legacy step (ms), per run | `device_batches` step (ms), per run | eager `device_optimizer` step (ms), per run | `graph_step` step (ms), per run | `device_optimizer` / `device_batches` (best of each) | `graph_step` / `device_batches` (best of each) | one `torch.randperm(n)` on the CPU (ms) |',
+             '|---|---|---|---|---|---|---|---|']
+    kern = ['', '## Kernel time of the batch launches (device events, mean of 200 calls; 50 for the draw)', '',
             '| n examples | `azg_train_sample_ids`, one epoch = n // batch steps (µs) | per step of that epoch (µs) | `azg_train_gather`, one batch (µs) | `azg_train_losses`, both launches (µs) |',
             '|---|---|---|---|---|']
     for n in [int(x) for x in args.sizes.split(',')]:
         ex = synthetic(n, dev)
-        legacy, device = [], []
+        runs = {name: [] for name, _ in PATHS}
         for _ in range(args.repeats):
-            legacy.append(time_path(ex, args.batch, args.warmup, args.steps, False))
-            device.append(time_path(ex, args.batch, args.warmup, args.steps, True))
+            for name, switches in PATHS:
+                runs[name].append(time_path(ex, args.batch, args.warmup, args.steps, switches))
         g = torch.Generator(device='cpu')
         g.manual_seed(1)
         torch.randperm(n, generator=g)
@@ -112,7 +119,10 @@ def main(argv=None):
             torch.randperm(n, generator=g)
         perm_ms = (time.perf_counter() - t0) / 10 * 1e3
         fmt = lambda xs: ' / '.join('%.3f' % x for x in xs)  # noqa: E731
-        lines.append('| %d | %s | %s | %.3f | %.3f |' % (n, fmt(legacy), fmt(device), min(device) / min(legacy), perm_ms))
+        best = {name: min(xs) for name, xs in runs.items()}
+        lines.append('| %d | %s | %s | %s | %s | %.3f | %.3f | %.3f |' % (
+            n, fmt(runs['legacy']), fmt(runs['device_batches']), fmt(runs['device_optimizer']), fmt(runs['graph_step']),
+            best['device_optimizer'] / best['device_batches'], best['graph_step'] / best['device_batches'], perm_ms))
         # the three launches on their own
         spe = n // args.batch
         ids = torch.empty((spe, args.batch), dtype=torch.int32, device=dev)
@@ -131,6 +141,31 @@ def main(argv=None):
              'that launch is outside the timed window, and its share of a step is the third column.)',
              '', '(The event figures include the Python wrapper\'s argument checks and, for the losses, its three buffer allocations between the',
              'launches: they are the cost of the call as the trainer makes it, an upper bound of the kernels\' own time.)']
+    # the optimiser on the V80 parameter set: the two new launches against torch's own AdamW step (its foreach launches, host included)
+    m = train.SplendorV80Module(num_players=2, dropout=0.0).to(dev)
+    params = [p for p in m.parameters() if p.requires_grad]
+    for p in params:
+        p.grad = torch.randn_like(p) * 1e-3
+    ref = torch.optim.AdamW(params, lr=3e-4)
+    t_ref = event_ms(ref.step)
+    grads = [p.grad.clone() for p in params]
+    mine = train.DeviceAdamW(params, 3e-4, 1000)
+    for p, gr in zip(params, grads):
+        p.grad = gr
+    mine.step()                                                          # the first step moves the gradients into the flat buffer
+
+    def both():
+        train.adamw_update(mine.segs, mine.chunks, mine.table, mine.step_counter)
+        train.adamw_step_advance(mine.step_counter)
+
+    t_both = event_ms(both)
+    t_upd = event_ms(lambda: train.adamw_update(mine.segs, mine.chunks, mine.table, mine.step_counter))
+    kern += ['', '## The optimiser step on the V80 parameter set (device events, mean of 200 calls)', '',
+             '%d parameter tensors, %d floats, %d workgroups of 2048 elements.' % (len(params), sum(p.numel() for p in params), mine.chunks.shape[0]), '',
+             '| `azg_train_adamw` alone (µs) | `azg_train_adamw` + `azg_train_step_advance` (µs) | `torch.optim.AdamW.step()`, foreach (µs) |', '|---|---|---|',
+             '| %.1f | %.1f | %.1f |' % (t_upd * 1e3, t_both * 1e3, t_ref * 1e3),
+             '', '(Back-to-back calls from Python: where the host issues slower than the GPU runs, the figure is the host\'s issue time per call,',
+             'an upper bound of the kernels\' own time.)']
     text = '\n'.join(lines + kern) + '\n'
     print(text)
     if args.out:

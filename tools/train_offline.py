@@ -8,7 +8,9 @@ With --training: the example history is flattened, the last tenth is held out as
 nb_samples * 1000 of the rest are trained on with the test set validated every 1e5 // batch_size - 1 steps (NNetWrapper.train: the forward
 of the validation on the engine's one-launch kernel, the losses by azg_eval_losses), intermediary_<i>.pt and at the end last.pt are written
 into <output><last six digits of the time>/.  Same flags and defaults as the reference; no FLOP count is printed (that needs fvcore).
---device-batches (not in the reference): the training batches are drawn, gathered and scored on the GPU, nothing is read back per step."""
+--device-batches (not in the reference): the training batches are drawn, gathered and scored on the GPU, nothing is read back per step.
+--device-optimizer / --graph-step (not in the reference; both need --device-batches): AdamW + OneCycleLR in one launch with the step number
+on the GPU / a whole training step as one replay of a captured graph."""
 import argparse
 import os
 import sys
@@ -44,6 +46,8 @@ def build_parser():
 def add_engine_options(parser):
     """options of the engine's trainer that are no flag of the reference's (build_parser keeps to those)"""
     parser.add_argument('--device-batches', action='store_true', help='Draw, gather and score the training batches on the GPU (train.train(device_batches=True)): no host synchronisation per step')
+    parser.add_argument('--device-optimizer', action='store_true', help='AdamW + OneCycleLR as one launch that takes the step number from device memory (train.train(device_optimizer=True)); needs --device-batches')
+    parser.add_argument('--graph-step', action='store_true', help='Capture one training step as a graph and replay it for every later step (train.train(graph_step=True)); implies --device-optimizer, needs --device-batches')
     return parser
 
 
@@ -80,7 +84,8 @@ def main(argv=None):
     output = (args.output if args.output else 'output_') + str(int(time.time()))[-6:]
     g = make_game(args)
     nn_args = dict(lr=args.learn_rate, dropout=args.dropout, epochs=args.epochs, batch_size=args.batch_size, nn_version=args.nn_version,
-                   learn_rate=args.learn_rate, no_compression=False, q_weight=args.q_weight, device_batches=args.device_batches)
+                   learn_rate=args.learn_rate, no_compression=False, q_weight=args.q_weight, device_batches=args.device_batches,
+                   device_optimizer=args.device_optimizer, graph_step=args.graph_step)
     nnet = NNetWrapper(g, nn_args)
     if args.input:
         nnet.load_checkpoint(os.path.dirname(args.input), os.path.basename(args.input))
