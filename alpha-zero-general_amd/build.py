@@ -21,7 +21,8 @@ UNITS = [('azg.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_async_sel.hip', ['-mllvm', '-disable-promote-alloca-to-lds'] + os.environ.get('AZG_ASYNC_SEL_FLAGS', '').split()),
          ('azg_playout.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_loss.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
-         ('azg_train.hip', ['-mllvm', '-disable-promote-alloca-to-lds'])]
+         ('azg_train.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
+         ('azg_examples.hip', ['-mllvm', '-disable-promote-alloca-to-lds'])]
 # (azg_async.hip / azg_async_sel.hip: the asynchronous tree pipeline, azg_async.hip.h -- the persistent net kernel + the C-ABI / the
 # persistent descent kernel.  -disable-machine-licm for the NET kernel only: it is ONE long loop around a body that fills the register
 # file; with machine LICM the compiler hoists address constants and zero vectors out of that loop and then spills them -- 34 spilled
@@ -31,6 +32,7 @@ UNITS = [('azg.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
 # (azg_playout.hip: the random-playout kernels, playout.hip.h -- a unit of its own so that they cannot change what is inlined into azg.hip's kernels)
 # (azg_loss.hip: the validation-loss kernels, loss.hip.h -- a unit of its own for the same reason)
 # (azg_train.hip: the training step's batch kernels, train.hip.h -- draw, gather, losses + gradients; a unit of its own for the same reason)
+# (azg_examples.hip: the example-expansion kernels, examples.hip.h -- records to dense example rows; a unit of its own for the same reason)
 # debugging builds: AZG_DEFINES="AZG_CYC_COUNTERS AZG_NN_PHASE_TIMES" python alpha-zero-general_amd/build.py
 FLAGS += ['-D' + d for d in os.environ.get('AZG_DEFINES', '').split()]
 FLAGS += os.environ.get('AZG_EXTRA_FLAGS', '').split()            # e.g. -ftrivial-auto-var-init=pattern when hunting an uninitialised local

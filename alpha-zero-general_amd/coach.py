@@ -55,15 +55,20 @@ def episode_share(num_eps, n_games, world, rank):
 
 
 class Coach:
-    def __init__(self, game, nnet, args, n_games=None, node_capacity=None, log=print, dist=None):
+    def __init__(self, game, nnet, args, n_games=None, node_capacity=None, log=print, dist=None, device_history=None):
         """n_games: concurrent self-play games over ALL ranks.  dist: None = use torch.distributed when it is initialised with more
-        than one rank; False = single process; True = go through the collectives even at world size 1"""
+        than one rank; False = single process; True = go through the collectives even at world size 1.
+        device_history (None = args.device_history, default False): rank 0 keeps the example history on the GPU (history.DeviceHistory):
+        an iteration's records are expanded into it in place (azg_examples_expand) and the trainer reads it in place, without a shuffle
+        -- the wrapper must train with nn_args['device_batches'].  args.examples_file then names the file saveTrainExamples writes:
+        'reference' (checkpoint.examples, the default), 'columns' (checkpoint.examples.npz) or 'none'"""
         self.game, self.args, self.log = game, args, log
         if not hasattr(nnet, 'save_checkpoint'):                     # a bare torch module: give it the NeuralNet surface
             engine_module = is_engine_module(nnet)
             w = NNetWrapper(game, dict(nn_version=getattr(nnet, 'version', -1), learn_rate=_get(args, 'learn_rate', 3e-3),
                                        batch_size=_get(args, 'batch_size', 512), epochs=_get(args, 'epochs', 2),
-                                       q_weight=_get(args, 'q_weight', 0.5), dropout=_get(args, 'dropout', 0.0)),
+                                       q_weight=_get(args, 'q_weight', 0.5), dropout=_get(args, 'dropout', 0.0),
+                                       device_batches=_get(args, 'device_batches', False)),
                             module=None if engine_module else nnet)
             if engine_module:
                 w.nnet = nnet
@@ -90,6 +95,16 @@ class Coach:
         self.iter_base = 0                   # like the number of iterations already played: a resumed run draws fresh randomness
         self._sym_stream = 0
         self.results = []
+        self.device_history = None
+        if bool(_get(args, 'device_history', False) if device_history is None else device_history):
+            if not _get(getattr(self.nnet, 'args', None) or {}, 'device_batches', False):
+                raise ValueError("Coach(device_history=True) needs a wrapper that trains with nn_args['device_batches']: the host trainer "
+                                 "draws its batches from another random stream, and the device history is never shuffled")
+            if _get(args, 'examples_file', 'reference') not in ('reference', 'columns', 'none'):
+                raise ValueError("args.examples_file must be 'reference', 'columns' or 'none', got %r" % (_get(args, 'examples_file', None),))
+            from .history import DeviceHistory
+            self.device_history = DeviceHistory(game.S, game.A, game.P, device=game.device)
+            self._ref_iters = []                 # per iteration of the device history: its deque in the reference's layout, or None
 
     # engine-side aliases kept from round 1
     @property
@@ -104,10 +119,12 @@ class Coach:
         return self.executeEpisodes(as_tensors=True)
 
     # ---- Coach.executeEpisodes (:86-148) ----
-    def executeEpisodes(self, as_tensors=False):
+    def executeEpisodes(self, as_tensors=False, to_history=False):
         """numEps finished games of self-play with the current net -> one iteration's examples (a deque in the reference's
         layout; as_tensors=True: device tensors (boards, pi, z, valids, q, meta) with the symmetries applied).  Collective when
-        the Coach is distributed: rank 0 returns the examples of ALL ranks (it trains, Coach.py:150-215), the other ranks return none."""
+        the Coach is distributed: rank 0 returns the examples of ALL ranks (it trains, Coach.py:150-215), the other ranks return none.
+        to_history=True (rank 0 of a Coach with a device history): the examples become the next iteration of self.device_history;
+        -> (rows kept, rows before the maxlenOfQueue cut)"""
         num_eps = int(_get(self.args, 'numEps', self.T))
         my_eps = episode_share(num_eps, self.T, self.world, self.rank)
         sims = int(_get(self.args, 'numMCTSSims', 800))
@@ -151,6 +168,8 @@ class Coach:
                 failure = 'self-play failed on another rank'
         if failure:
             raise RuntimeError(failure)
+        if to_history:
+            return self._append_to_history(parts)
         ex = self._collect(parts)
         if as_tensors:
             return ex
@@ -195,6 +214,31 @@ class Coach:
         rep = torch.repeat_interleave(torch.arange(boards.shape[0], device=cnt.device), cnt.to(torch.int64))
         return (ob.reshape(-1, ob.shape[2])[keep], op.reshape(-1, op.shape[2])[keep], z[rep], ov.reshape(-1, ov.shape[2])[keep], q[rep], meta[rep])
 
+    def _append_to_history(self, parts):
+        """rank 0's form of _collect with a device history: the same gather, then the records go into the history's rows
+        (DeviceHistory.append_records: canonical order, every symmetric form, the symmetry streams _collect would use)"""
+        from .selfplay import gather_examples
+        if parts:
+            ex = [torch.cat([p[i] for p in parts], dim=0) for i in range(6)]
+        else:
+            dev, S, A, P = self.game.device, self.game.S, self.game.A, self.game.P
+            ex = [torch.empty((0, w), dtype=dt, device=dev) for w, dt in ((S, torch.int8), (A, torch.float32), (P, torch.float32),
+                                                                          (A, torch.uint8), (P, torch.float32), (4, torch.int32))]
+        if self.dist:
+            info = {}
+            ex = gather_examples(ex, dst=0, info=info)
+            self.last_gather = info
+        h = self.device_history
+        kept, total = h.append_records(self.game, ex, maxlen=int(_get(self.args, 'maxlenOfQueue', 10 ** 6)), stream0=(1 << 42) + self._sym_stream)
+        self._sym_stream += int(ex[0].shape[0])
+        self._ref_iters.append(None)
+        alpha = float(_get(self.args, 'dirichletAlpha', 0) or 0)
+        if kept and alpha > 0:                                                 # Coach.py:169-176
+            avg_valid_moves = float(h.iteration_columns(-1)[3].sum(dtype=torch.int64).item()) / kept
+            if not (1 / 1.5 < alpha / (10 / avg_valid_moves) < 1.5):
+                self.log('There are about %.1f valid moves per state, so I advise to set dirichlet to %.1f instead' % (avg_valid_moves, 10 / avg_valid_moves))
+        return kept, total
+
     # ---- weights across ranks ----
     def _broadcast_weights(self, module, src=0):
         """rank `src`'s parameters and buffers -> every rank, as one flat tensor per dtype (a few hundred KB .. 2 MB)"""
@@ -235,7 +279,11 @@ class Coach:
         for i in range(1, int(_get(a, 'numIters', 1)) + 1):
             it = self.iter_base + i
             if not self.skipFirstSelfPlay or i > 1:
-                if lead:
+                if lead and self.device_history is not None:
+                    kept, _ = self.executeEpisodes(to_history=True)
+                    if kept == int(_get(a, 'maxlenOfQueue', 10 ** 6)):
+                        self.log('saturation of elements in iterationTrainExamples, think about decreasing numEps or increasing maxlenOfQueue')
+                elif lead:
                     it_examples = self.executeEpisodes()
                     if len(it_examples) == int(_get(a, 'maxlenOfQueue', 10 ** 6)):
                         self.log('saturation of elements in iterationTrainExamples, think about decreasing numEps or increasing maxlenOfQueue')
@@ -248,13 +296,20 @@ class Coach:
             # the competitor = the net before training (Coach.py:188-189 goes through temp.pt; rank 0 writes that file, every rank
             # copies the weights in memory)
             if lead:
+                if self.device_history is not None and len(self.device_history) > int(_get(a, 'numItersHistory', 5)):
+                    self.device_history.pop_oldest()
+                    self._ref_iters.pop(0)
                 if len(self.trainExamplesHistory) > int(_get(a, 'numItersHistory', 5)):
                     self.trainExamplesHistory.pop(0)
                 self.saveTrainExamples(iterations_done=it)                                                # :180
                 self.nnet.save_checkpoint(folder=ckpt, filename='temp.pt', additional_keys=extra)         # :188
             self._copy_weights(self.nnet, self.pnet)
             n_examples = 0
-            if lead:
+            if lead and self.device_history is not None:
+                # the device sampler draws without replacement from the whole set: row order carries no meaning, nothing is shuffled
+                n_examples = self.device_history.n
+                self.nnet.train(self.device_history.columns(), log=self.log, seed=None if seed is None else int(seed) + it)
+            elif lead:
                 train_examples = [e for h in self.trainExamplesHistory for e in h]
                 (random.Random(int(seed) * 1000003 + it) if seed is not None else random).shuffle(train_examples)     # :185
                 n_examples = len(train_examples)
@@ -321,7 +376,17 @@ class Coach:
     def saveTrainExamples(self, iterations_done=None):                                                # :220-226
         folder = _get(self.args, 'checkpoint', './checkpoint')
         os.makedirs(folder, exist_ok=True)
-        formats.save_train_examples(os.path.join(folder, 'checkpoint.examples'), self.trainExamplesHistory)
+        if self.device_history is None:
+            formats.save_train_examples(os.path.join(folder, 'checkpoint.examples'), self.trainExamplesHistory)
+        elif _get(self.args, 'examples_file', 'reference') == 'reference':
+            # every iteration is encoded once, when it is first saved; its deque stays on the host for the saves that follow
+            for j, it in enumerate(self._ref_iters):
+                if it is None:
+                    self._ref_iters[j] = self.device_history.to_reference(j, self.game.getBoardSize(), compress=not _get(self.args, 'no_compression', False),
+                                                                          maxlen=int(_get(self.args, 'maxlenOfQueue', 10 ** 6)))
+            formats.save_train_examples(os.path.join(folder, 'checkpoint.examples'), self._ref_iters)
+        elif _get(self.args, 'examples_file', 'reference') == 'columns':
+            self.device_history.save_columns(os.path.join(folder, 'checkpoint.examples.npz'))
         # engine-side state next to the reference's file: where the random streams of a resumed run continue (the reference draws
         # fresh OS randomness on every start; a seeded engine would replay iteration 1's boards, chance outcomes and noise)
         with open(os.path.join(folder, 'azg_state.json'), 'w') as f:
@@ -334,6 +399,8 @@ class Coach:
         path = os.path.join(os.path.dirname(model_file or ''), 'checkpoint.examples')
         if self.rank != 0:
             return          # rank 0 keeps the history and trains; its resume state reaches the other ranks in learn() (_sync_resume_state)
+        if self.device_history is not None:
+            return self._load_device_history(path)
         if not os.path.isfile(path):
             self.log('File "%s" with trainExamples not found!' % path)
             return
@@ -362,7 +429,51 @@ class Coach:
             while len(it) > maxlen:
                 it.pop()
 
-    def temp_for_game(self, n):                                                                       # :273-276
+    def _load_device_history(self, path):
+        """loadTrainExamples into the device history: checkpoint.examples.npz when args.examples_file is 'columns' and the file is there,
+        else checkpoint.examples (this engine's or the reference's); the same azg_state.json, numItersHistory and maxlenOfQueue handling"""
+        from .history import DeviceHistory
+        n_hist, maxlen = int(_get(self.args, 'numItersHistory', 5)), int(_get(self.args, 'maxlenOfQueue', 10 ** 6))
+        if _get(self.args, 'examples_file', 'reference') == 'columns' and os.path.isfile(path + '.npz'):
+            h = DeviceHistory.load_columns(path + '.npz', device=self.game.device)
+            if h.widths != self.device_history.widths:
+                raise ValueError('%s.npz holds columns of widths %r, this game has %r' % (path, h.widths, self.device_history.widths))
+            n_loaded = len(h)
+            while len(h) > n_hist:                                                                    # :254-256
+                h.pop_oldest()
+            for j in range(len(h)):                                                                   # :257-261 (drops from the END)
+                h.truncate_iteration(j, maxlen)
+            refs = [None] * len(h)
+        elif os.path.isfile(path):
+            with open(path, 'rb') as f:
+                refs = pickle.load(f)
+            n_loaded = len(refs)
+            want_raw = bool(_get(self.args, 'no_compression', False))
+            for it in refs:                                                                           # :243-250
+                for j in range(len(it)):
+                    if isinstance(it[j], tuple) and not want_raw:
+                        it[j] = zlib.compress(pickle.dumps(it[j]), level=1)
+                    elif not isinstance(it[j], tuple) and want_raw:
+                        it[j] = pickle.loads(zlib.decompress(it[j]))
+            refs = refs[-n_hist:] if len(refs) > n_hist else refs
+            for it in refs:
+                while len(it) > maxlen:
+                    it.pop()
+            h = DeviceHistory.from_reference(refs, device=self.game.device, widths=(self.game.S, self.game.A, self.game.P))
+        else:
+            self.log('File "%s" with trainExamples not found!' % path)
+            return
+        self.device_history, self._ref_iters = h, list(refs)
+        state = os.path.join(os.path.dirname(path), 'azg_state.json')
+        if os.path.isfile(state):                                        # continue the random streams where the saved run stopped
+            with open(state) as f:
+                st = json.load(f)
+            self.n_selfplay_waves, self.iter_base = int(st.get('selfplay_waves', 0)), int(st.get('iterations_done', 0))
+            self._sym_stream = int(st.get('sym_stream', 0))
+        else:                                                            # a history written by the reference: start behind it
+            self.n_selfplay_waves = self.iter_base = n_loaded
+
+    def temp_for_game(self, n):                                                                    # :273-276
         t_begin, t_end, half_life = 0.5, 0.0, abs(float(_get(self.args, 'tempThreshold', 10)))
         return t_end + (t_begin - t_end) * (0.5 ** (n / half_life))
 

@@ -1,0 +1,142 @@
+// examples.hip.h -- one iteration's drained records -> the dense rows of the five example columns in ONE launch (azg_examples_expand):
+// Coach.executeEpisode's `for sym in getSymmetries(...)` (Coach.py:66-69) for n records at once, written where the trainer reads them.
+// One workgroup = one 64-lane wave = one group (record), exactly as k_env_symmetries / k_env_symmetries_built (kernels.hip.h) hold it: the
+// state in LDS, the forms through the same G::sym_exists / sym_state_byte / sym_action_src and G::sym_build (+ SYM_DEDUP) interfaces, in
+// the same order and with the same draws.  What differs is where a form goes: form k of group g is ROW first_row[g] + k of the outputs
+// (no [n][K][.] intermediate, no mask pass), z and q of the source record are replicated into the row, and only rows inside
+// [row_begin, row_end) are written -- a form outside the window is still built, counted and, where the game draws, paid for in draws.
+// first_row == NULL is the count pass: the same loop without a store.
+// States are stored as dwords (4 bytes per lane, 256 B per wave instruction) where S is a multiple of 4 and the buffer is 4-byte aligned
+// -- every row then starts on a dword --, as single bytes otherwise; the bytes are the same either way.
+#pragma once
+#include "forest.hip.h"
+
+namespace azg {
+
+struct ExamplesOut {
+    int8_t* states; float* pi; float* z; uint8_t* valids; float* q;      // row-major [rows][S | A | P | A | P]
+    int64_t row_begin, row_end;                                           // the only rows that may be written
+    int wide;                                                             // states 4-byte aligned: dword stores where S % 4 == 0
+};
+
+// 4 consecutive bytes of form c, as the byte stores would leave them in memory (little endian)
+template <class G>
+__device__ __forceinline__ uint32_t examples_state_dword(const int8_t* st, int c, int i) {
+    return (uint32_t)(uint8_t)G::sym_state_byte(st, c, i) | ((uint32_t)(uint8_t)G::sym_state_byte(st, c, i + 1) << 8) |
+           ((uint32_t)(uint8_t)G::sym_state_byte(st, c, i + 2) << 16) | ((uint32_t)(uint8_t)G::sym_state_byte(st, c, i + 3) << 24);
+}
+
+// z and q of the source record into row `row`
+template <class G>
+__device__ __forceinline__ void examples_store_zq(const ExamplesOut& o, int64_t row, const float* zin, const float* qin) {
+    if (lane_id() < G::P) {
+        o.z[row * G::P + lane_id()] = zin[lane_id()];
+        o.q[row * G::P + lane_id()] = qin[lane_id()];
+    }
+}
+
+// Games whose forms are byte and action maps of the state (k_env_symmetries).
+template <class G>
+__global__ __launch_bounds__(64) void k_examples_expand(const int8_t* states, const float* pi, const float* z, const uint8_t* valids,
+                                                         const float* q, int n, const int32_t* order, const int64_t* first_row,
+                                                         ExamplesOut o, int32_t* out_count) {
+    __shared__ __attribute__((aligned(16))) int8_t st[G::SP];
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int src_rec = order ? order[g] : g;
+    if ((unsigned)src_rec >= (unsigned)n) {                  // an order entry outside [0, n): no form, nothing read
+        if (lane_id() == 0) out_count[g] = 0;
+        return;
+    }
+    Forest<G>::load_state_unpadded(st, states + (size_t)src_rec * G::S);
+    const float* pin = pi + (size_t)src_rec * G::A;
+    const uint8_t* vin = valids + (size_t)src_rec * G::A;
+    const bool write = first_row != nullptr;
+    const int64_t row0 = write ? first_row[g] : 0;
+    int k = 0;
+    for (int c = 0; c < G::NSYM_CAND; c++) {
+        if (!G::sym_exists(st, c)) continue;
+        const int64_t row = row0 + k;
+        if (write && row >= o.row_begin && row < o.row_end) {
+            if (G::S % 4 == 0 && o.wide) {
+                uint32_t* dst = (uint32_t*)(o.states + row * G::S);
+                for (int i = lane_id(); i < G::S / 4; i += 64) dst[i] = examples_state_dword<G>(st, c, 4 * i);
+            } else {
+                for (int i = lane_id(); i < G::S; i += 64) o.states[row * G::S + i] = G::sym_state_byte(st, c, i);
+            }
+            for (int a = lane_id(); a < G::A; a += 64) {
+                const int src = G::sym_action_src(st, c, a);          // < 0: no action maps onto a (Abalone groups off the grid)
+                o.pi[row * G::A + a] = src >= 0 ? pin[src] : 0.f;
+                o.valids[row * G::A + a] = src >= 0 ? vin[src] : (uint8_t)0;
+            }
+            examples_store_zq<G>(o, row, z + (size_t)src_rec * G::P, q + (size_t)src_rec * G::P);
+        }
+        k++;
+    }
+    if (lane_id() == 0) out_count[g] = k;
+}
+
+// Games whose forms are BUILT by lane 0 (G::RANDOM_SYM, k_env_symmetries_built): group g draws from the counter stream
+// (rng_seed, stream0 + g) -- the GROUP index, whatever source record `order` names.
+template <class G>
+__global__ __launch_bounds__(64) void k_examples_expand_built(const int8_t* states, const float* pi, const float* z, const uint8_t* valids,
+                                                               const float* q, int n, const int32_t* order, const int64_t* first_row,
+                                                               ExamplesOut o, int32_t* out_count, uint64_t rng_seed, uint64_t stream0) {
+    constexpr int NKEEP = G::SYM_DEDUP ? G::NSYM_CAND : 1;
+    __shared__ __attribute__((aligned(16))) int8_t st[G::SP];
+    __shared__ __attribute__((aligned(16))) int8_t kept[NKEEP][G::SP];
+    __shared__ int16_t act_src[G::A];
+    __shared__ int exists_s;
+    const int g = blockIdx.x;
+    if (g >= n) return;
+    const int src_rec = order ? order[g] : g;
+    if ((unsigned)src_rec >= (unsigned)n) {
+        if (lane_id() == 0) out_count[g] = 0;
+        return;
+    }
+    Forest<G>::load_state_unpadded(st, states + (size_t)src_rec * G::S);
+    const float* pin = pi + (size_t)src_rec * G::A;
+    const uint8_t* vin = valids + (size_t)src_rec * G::A;
+    const bool write = first_row != nullptr;
+    const int64_t row0 = write ? first_row[g] : 0;
+    Rng rng{rng_seed, stream0 + (uint64_t)g, 0};
+    int k = 0;
+    for (int c = 0; c < G::NSYM_CAND; c++) {
+        int8_t* cand = kept[G::SYM_DEDUP ? (k < NKEEP ? k : NKEEP - 1) : 0];
+        for (int i = lane_id(); i < G::S; i += 64) cand[i] = st[i];
+        __syncthreads();
+        if (lane_id() == 0) exists_s = G::sym_build(st, c, cand, act_src, rng, vin) ? 1 : 0;     // (draws even when the form is dropped below)
+        __syncthreads();
+        bool keep = exists_s != 0;
+        if (keep && G::SYM_DEDUP) {
+            for (int e = 0; e < k && keep; e++) {
+                bool diff = false;
+                for (int i = lane_id(); i < G::S; i += 64) diff |= kept[e][i] != cand[i];
+                keep = __ballot(diff) != 0;
+            }
+        }
+        if (keep) {
+            const int64_t row = row0 + k;
+            if (write && row >= o.row_begin && row < o.row_end) {
+                if (G::S % 4 == 0 && o.wide) {                       // (cand is 16-byte aligned: G::SP is a multiple of 16)
+                    uint32_t* dst = (uint32_t*)(o.states + row * G::S);
+                    const uint32_t* cw = (const uint32_t*)cand;
+                    for (int i = lane_id(); i < G::S / 4; i += 64) dst[i] = cw[i];
+                } else {
+                    for (int i = lane_id(); i < G::S; i += 64) o.states[row * G::S + i] = cand[i];
+                }
+                for (int a = lane_id(); a < G::A; a += 64) {
+                    const int src = act_src[a];                      // < 0: nothing maps onto a
+                    o.pi[row * G::A + a] = src >= 0 ? pin[src] : 0.f;
+                    o.valids[row * G::A + a] = src >= 0 ? vin[src] : (uint8_t)0;
+                }
+                examples_store_zq<G>(o, row, z + (size_t)src_rec * G::P, q + (size_t)src_rec * G::P);
+            }
+            k++;
+        }
+        __syncthreads();
+    }
+    if (lane_id() == 0) out_count[g] = k;
+}
+
+}  // namespace azg

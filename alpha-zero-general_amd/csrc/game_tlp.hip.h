@@ -256,62 +256,64 @@ struct TLPDev {
     // ---- get_symmetries :177-272.  Candidate 0 is the identity; 1..n shuffle the players who already played / who have not
     // (two shuffles, the current player stays); n+1..2n shuffle the market cards and, per player and card type, the planet slots
     // (pi and valids come back unpermuted for these, as written :223,237).  Every form is a row map of the input because the
-    // chained shuffles act on disjoint rows.  lane 0 draws and fills row_src[ROWS] / act_src[A]; the kernel applies them and
-    // drops states equal to a form already kept (_add_to_list_no_duplicate :239-244).
+    // chained shuffles act on disjoint rows.  lane 0 draws, copies the mapped rows of the input into the candidate and fills
+    // act_src[A]; the kernel drops states equal to a form already kept (_add_to_list_no_duplicate :239-244).
+    // The lists that are shuffled hold at most 16 entries below 16 (players, market cards, planet slots): one 64-bit word of 4-bit
+    // entries each, so that nothing of lane 0's work is a private array with a run-time index (scratch memory).
     static constexpr int NSYM_CAND = 2 * NP + 1;
-    __device__ static void shuffle(Rng& rng, int* a, int len) {
+    __device__ static __forceinline__ int nib(uint64_t v, int i) { return (int)((v >> (4 * i)) & 15ull); }
+    __device__ static __forceinline__ uint64_t nib_put(uint64_t v, int i, int x) {
+        return (v & ~(15ull << (4 * i))) | ((uint64_t)x << (4 * i));
+    }
+    __device__ static uint64_t shuffle(Rng& rng, uint64_t a, int len) {
         for (int i = len - 1; i > 0; i--) {
             int j = (int)(rng.u01() * (double)(i + 1));
             j = j > i ? i : j;
-            const int t = a[i]; a[i] = a[j]; a[j] = t;
+            const int ti = nib(a, i), tj = nib(a, j);
+            a = nib_put(nib_put(a, i, tj), j, ti);
         }
+        return a;
     }
-    __device__ static void sym_random_maps(const int8_t* st, int cand, int16_t* row_src, int16_t* act_src, Rng& rng) {
-        for (int r = 0; r < ROWS; r++) row_src[r] = (int16_t)r;
-        for (int a = 0; a < A; a++) act_src[a] = (int16_t)a;
-        int list[16], sh[16];
-        if (cand <= NP) {
-            const int cur = st[1];
-            for (int pass = 0; pass < 2; pass++) {                             // players who played, then those who have not
-                int len = 0;
-                for (int i = 0; i < NP; i++)
-                    if (i != cur && can_play(st, i) == (pass == 1)) { list[len] = i; sh[len] = i; len++; }
-                shuffle(rng, sh, len);
-                for (int i = 0; i < len; i++) {
-                    const int o = list[i], w = sh[i];
-                    row_src[R_SCORE + w] = (int16_t)(R_SCORE + o);
-                    for (int c = 0; c < 16; c++) row_src[R_CARDS + 16 * w + c] = (int16_t)(R_CARDS + 16 * o + c);
-                    for (int c = 0; c < NP; c++) act_src[c * NP + w] = (int16_t)(c * NP + o);
-                }
-            }
-            return;
-        }
-        int len = 0;
-        for (int i = 0; i < NP; i++)
-            if (ctype(st, R_MARKET + i) != 0) { list[len] = i; sh[len] = i; len++; }
-        shuffle(rng, sh, len);
-        for (int i = 0; i < len; i++) row_src[R_MARKET + sh[i]] = (int16_t)(R_MARKET + list[i]);
-        for (int p = 0; p < NP; p++)
-            for (int ct = 1; ct <= 4; ct++) {
-                len = 0;
-                for (int i = 0; i < 16; i++)
-                    if (ctype(st, R_CARDS + 16 * p + i) / 25 == ct) { list[len] = i; sh[len] = i; len++; }
-                shuffle(rng, sh, len);
-                for (int i = 0; i < len; i++) row_src[R_CARDS + 16 * p + sh[i]] = (int16_t)(R_CARDS + 16 * p + list[i]);
-            }
+    __device__ static __forceinline__ void copy_row(int8_t* cand, const int8_t* st, int dst, int src) {
+        for (int k = 0; k < COLS; k++) cand[dst * COLS + k] = st[src * COLS + k];
     }
     // lane 0: `cand` (a copy of the input state) becomes form c
     __device__ static bool sym_build(const int8_t* st, int c, int8_t* cand, int16_t* act_src, Rng& rng, const uint8_t* valids) {
         (void)valids;
-        int16_t row_src[ROWS];
-        if (c == 0) {
-            for (int a = 0; a < A; a++) act_src[a] = (int16_t)a;
+        for (int a = 0; a < A; a++) act_src[a] = (int16_t)a;
+        if (c == 0) return true;
+        if (c <= NP) {
+            const int cur = st[1];
+            for (int pass = 0; pass < 2; pass++) {                             // players who played, then those who have not
+                uint64_t list = 0;
+                int len = 0;
+                for (int i = 0; i < NP; i++)
+                    if (i != cur && can_play(st, i) == (pass == 1)) { list = nib_put(list, len, i); len++; }
+                const uint64_t sh = shuffle(rng, list, len);
+                for (int i = 0; i < len; i++) {
+                    const int o = nib(list, i), w = nib(sh, i);
+                    copy_row(cand, st, R_SCORE + w, R_SCORE + o);
+                    for (int k = 0; k < 16; k++) copy_row(cand, st, R_CARDS + 16 * w + k, R_CARDS + 16 * o + k);
+                    for (int k = 0; k < NP; k++) act_src[k * NP + w] = (int16_t)(k * NP + o);
+                }
+            }
             return true;
         }
-        sym_random_maps(st, c, row_src, act_src, rng);
-        for (int r = 0; r < ROWS; r++)
-            if (row_src[r] != r)
-                for (int k = 0; k < COLS; k++) cand[r * COLS + k] = st[row_src[r] * COLS + k];
+        uint64_t list = 0;
+        int len = 0;
+        for (int i = 0; i < NP; i++)
+            if (ctype(st, R_MARKET + i) != 0) { list = nib_put(list, len, i); len++; }
+        uint64_t sh = shuffle(rng, list, len);
+        for (int i = 0; i < len; i++) copy_row(cand, st, R_MARKET + nib(sh, i), R_MARKET + nib(list, i));
+        for (int p = 0; p < NP; p++)
+            for (int ct = 1; ct <= 4; ct++) {
+                list = 0;
+                len = 0;
+                for (int i = 0; i < 16; i++)
+                    if (ctype(st, R_CARDS + 16 * p + i) / 25 == ct) { list = nib_put(list, len, i); len++; }
+                sh = shuffle(rng, list, len);
+                for (int i = 0; i < len; i++) copy_row(cand, st, R_CARDS + 16 * p + nib(sh, i), R_CARDS + 16 * p + nib(list, i));
+            }
         return true;
     }
     // (the deterministic interface is unused: k_env_symmetries takes the RANDOM_SYM path)

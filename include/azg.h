@@ -214,6 +214,29 @@ int azg_train_adamw(const azg_adamw_seg* segs_dev, int n_segs, const azg_adamw_c
 /* *step_dev += 1 in a one-wave launch of its own: enqueued behind azg_train_adamw, no workgroup of the update can see the new value. */
 int azg_train_step_advance(int64_t* step_dev, void* stream);
 
+/* ---- an iteration's records -> dense example rows, one launch (one wavefront per record) --------------------------------------------
+   Replaces Coach.executeEpisode's loop over getSymmetries (Coach.py:66-69) for n drained records: group g expands source record
+   order_dev[g] (NULL: record g) into its symmetric forms -- the forms, their order (identity first) and their number are those of
+   azg_env_symmetries_ex with max_sym = the game's maximum -- and form k becomes ROW first_row_dev[g] + k of the five output columns:
+   out_states int8[rows][S], out_pi f32[rows][A], out_valids u8[rows][A], and the record's z / q replicated into out_z / out_q
+   f32[rows][P].  Only rows inside [row_begin, row_end) are written; a form whose row lies outside (first_row_dev may be negative) is
+   skipped, but it is still counted and still consumes its draws.  out_count_dev int32[n] = the forms of group g, window or not.
+   first_row_dev == NULL is the COUNT pass: nothing but out_count_dev is written (the output columns may be NULL) and the counts are
+   those of the write pass, draws included; the caller's prefix sum over them gives first_row_dev.
+   Games with random forms draw group g from the RNG contract's stream (rng_seed, stream0 + g), counter from 0 -- the GROUP index, not
+   the source record's: a caller that reorders with order_dev gets the streams of the same call on pre-permuted inputs.
+   An order_dev entry outside [0, n) gives the group no form (count 0) and reads nothing.  n == 0 launches nothing.  NULL inputs with
+   n > 0, a NULL output column in a write pass with a non-empty window, an unknown game / variant or row_end < row_begin is an error
+   and launches nothing.  No synchronisation and no allocation. */
+int azg_examples_expand(int game, int variant,
+                        const int8_t* states_dev, const float* pi_dev, const float* z_dev, const uint8_t* valids_dev, const float* q_dev, int n,
+                        const int32_t* order_dev,       /* NULL or int32[n]: group g expands source record order[g] */
+                        const int64_t* first_row_dev,   /* NULL = count only; else int64[n]: destination row of form 0 of group g (may be negative) */
+                        int64_t row_begin, int64_t row_end,   /* only rows in [row_begin, row_end) are ever written */
+                        int8_t* out_states_dev, float* out_pi_dev, float* out_z_dev, uint8_t* out_valids_dev, float* out_q_dev,
+                        int32_t* out_count_dev,         /* int32[n]: forms of group g, in both modes */
+                        uint64_t rng_seed, uint64_t stream0, void* stream);
+
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */
 typedef struct azg_forest_cfg {
