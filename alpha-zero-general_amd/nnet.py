@@ -23,6 +23,12 @@ def _fold_bn(sd, prefix, eps=1e-5):
     return s, b - m * s
 
 
+def _wide(dtype):
+    """the dtype a plain-torch net folds its BatchNorms in and returns pi / v in: f32, or f64 for a float64 net (the f64 evaluation of
+    a net is the reference the kernels are held to: it must not carry f32 folds or an f32 softmax)"""
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
@@ -203,7 +209,7 @@ class SplendorV80(_TorchNet):
     """forward(board int8/float [B,56,7], valid bool [B,81]) -> (pi probabilities f32 [B,81], v f32 [B,P])."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.P = num_players
         self.nb_vect = 32 + 10 * num_players + num_players * num_players
         self.A = 81
@@ -272,9 +278,9 @@ class SplendorV80(_TorchNet):
         x = torch.matmul(x, self.W0) + self.b0                                                 # first_layer (+BN)
         x = self.trunk(x)
         hp = self.head_pi(x).reshape(B, -1)
-        logits = torch.addmm(self.bpi2, F.relu(torch.addmm(self.bpi1, hp, self.Wpi1)), self.Wpi2).float()
+        logits = torch.addmm(self.bpi2, F.relu(torch.addmm(self.bpi1, hp, self.Wpi1)), self.Wpi2).to(_wide(self.dtype))
         hv = self.head_v(x).reshape(B, -1)
-        v = torch.tanh(torch.addmm(self.bv2, F.relu(torch.addmm(self.bv1, hv, self.Wv1)), self.Wv2).float())
+        v = torch.tanh(torch.addmm(self.bv2, F.relu(torch.addmm(self.bv1, hv, self.Wv1)), self.Wv2).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))            # SplendorNNet.py:404
         pi = torch.softmax(logits, dim=1)              # exp(log_softmax) of GenericNNetWrapper.py:107,119
         return pi.contiguous(), v.contiguous()
@@ -370,7 +376,7 @@ class AzulV84(SplendorV80):
     23->115->23, policy head block 23->115->46 (no residual) + Linear(276,180)+ReLU+Linear, value head block 23->46->23."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.P = num_players
         self.nb_vect, self.L, self.A = 23, 6, 180
         s, b = _fold_bn(sd, 'first_layer.norm')
@@ -396,9 +402,9 @@ class AzulV84(SplendorV80):
         x = torch.matmul(x, self.W0) + self.b0
         x = self.trunk(x)
         hp = self.head_pi(x).reshape(B, -1)
-        logits = torch.addmm(self.bpi2, F.relu(torch.addmm(self.bpi1, hp, self.Wpi1)), self.Wpi2).float()
+        logits = torch.addmm(self.bpi2, F.relu(torch.addmm(self.bpi1, hp, self.Wpi1)), self.Wpi2).to(_wide(self.dtype))
         hv = self.head_v(x).reshape(B, -1)
-        v = torch.tanh(torch.addmm(self.bv2, F.relu(torch.addmm(self.bv1, hv, self.Wv1)), self.Wv2).float())
+        v = torch.tanh(torch.addmm(self.bv2, F.relu(torch.addmm(self.bv1, hv, self.Wv1)), self.Wv2).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -414,7 +420,7 @@ class MobileNet1d(AzulV84):
     (TLP nn_version 80 / 82 differ in the expansion factor only and load the same way.)"""
 
     def __init__(self, state_dict, num_players=None, head_se='max', device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.nb_vect = int(sd['first_layer.linear.weight'].shape[0])
         self.L = L = int(sd['trunk.0.depthwise.linear.weight'].shape[0])
         self.A = int(sd['output_layers_PI.4.weight'].shape[0])
@@ -528,7 +534,7 @@ class SantoriniV89(_TorchNet):
     BatchNorm folded into the convolutions (eval mode); plain torch ops (MIOpen / hipBLASLt)."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.P, self.A = num_players, sd['head_PI.fc.weight'].shape[0]
 
         def conv_bn(conv, bn):
@@ -565,9 +571,9 @@ class SantoriniV89(_TorchNet):
             y = F.relu(F.conv2d(x, w1, b1, padding=1))
             x = F.relu(F.conv2d(y, w2, b2, padding=1) + x)
         hp = F.relu(F.conv2d(x, self.hp[0], self.hp[1])).flatten(1)
-        logits = torch.addmm(self.fc_pi[1], hp, self.fc_pi[0]).float()
+        logits = torch.addmm(self.fc_pi[1], hp, self.fc_pi[0]).to(_wide(self.dtype))
         hv = F.relu(F.conv2d(x, self.hv[0], self.hv[1])).flatten(1)
-        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).float())
+        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -634,7 +640,7 @@ class SantoriniV78(SantoriniV89):
     (eps 1e-5) folded into the convolutions; plain torch ops."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.P, self.A = num_players, sd['head_PI.fc.weight'].shape[0]
 
         def conv_bn(conv, bn):
@@ -673,9 +679,9 @@ class SantoriniV78(SantoriniV89):
             h = F.relu(F.conv2d(h, wd, bd, padding=1, groups=wd.shape[0]))
             x = F.conv2d(h, wp, bp) + x
         hp = torch.cat([F.relu(F.conv2d(x, self.hp[0], self.hp[1])).flatten(1), meta], dim=1)
-        logits = torch.addmm(self.fc_pi[1], hp, self.fc_pi[0]).float()
+        logits = torch.addmm(self.fc_pi[1], hp, self.fc_pi[0]).to(_wide(self.dtype))
         hv = torch.cat([F.relu(F.conv2d(x, self.hv[0], self.hv[1])).flatten(1), meta], dim=1)
-        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).float())
+        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -758,7 +764,7 @@ class AbaloneV21(_TorchNet):
     embedding of the 6 metadata values (Linear(6,16)+ReLU), -> 64 -> P.  BatchNorm (eps 1e-5) folded; plain torch ops."""
 
     def __init__(self, state_dict, num_players=2, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.P, self.A = num_players, 81 * sd['head_PI.0.weight'].shape[0]
 
         def conv_bn(conv, bn):
@@ -795,9 +801,9 @@ class AbaloneV21(_TorchNet):
             h = F.relu(F.conv2d(x, we, be))
             h = F.relu(F.conv2d(h, wd, bd, padding=1, groups=wd.shape[0]))
             x = F.conv2d(h, wp, bp) + x
-        logits = F.conv2d(x, self.hp[0], self.hp[1]).permute(0, 2, 3, 1).reshape(B, self.A).float()
+        logits = F.conv2d(x, self.hp[0], self.hp[1]).permute(0, 2, 3, 1).reshape(B, self.A).to(_wide(self.dtype))
         hv = torch.cat([F.relu(F.conv2d(x, self.hv[0], self.hv[1])).flatten(1), meta], dim=1)
-        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).float())
+        v = torch.tanh(torch.addmm(self.fc_v2[1], F.relu(torch.addmm(self.fc_v1[1], hv, self.fc_v1[0])), self.fc_v2[0]).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -917,8 +923,8 @@ class SmallworldV62(_TorchNet):
         loc = F.linear(x[:, :nA], *self.local)                                                           # [B][nA][5]
         g = x[:, nA:].mean(dim=1)
         gl = F.linear(g, *self.glob)
-        logits = torch.cat([loc[..., 0], loc[..., 1], loc[..., 2], loc[..., 3], gl[:, 0:8], loc[..., 4], gl[:, 8:16]], dim=1).float()
-        v = torch.tanh(F.linear(g, *self.value).float())
+        logits = torch.cat([loc[..., 0], loc[..., 1], loc[..., 2], loc[..., 3], gl[:, 0:8], loc[..., 4], gl[:, 8:16]], dim=1).to(_wide(self.dtype))
+        v = torch.tanh(F.linear(g, *self.value).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -1055,9 +1061,9 @@ class AkropolisV31(_TorchNet):
         p = (d * sc[:, None]) @ self.wp + self.bp                                           # [B][169][16]
         a = F.hardswish(f3 @ self.wi + self.bi)                                             # [B][CS][16]
         wc = a[:, :, None, :] * (f3 @ self.wo + self.bo).view(B, CS, 6, 16)               # W_c [B][CS][6][16]
-        logits = torch.einsum('bnr,bcor->bcno', p, wc).reshape(B, self.A).float()
+        logits = torch.einsum('bnr,bcor->bcno', p, wc).reshape(B, self.A).to(_wide(self.dtype))
         v = F.hardswish(f3.reshape(B, CS * 56) @ self.wv1 + self.bv1)
-        v = torch.tanh((F.hardswish(v @ self.wv2 + self.bv2) @ self.wv3 + self.bv3).float())
+        v = torch.tanh((F.hardswish(v @ self.wv2 + self.bv2) @ self.wv3 + self.bv3).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 
@@ -1143,7 +1149,7 @@ class BotanikV1x(_TorchNet):
     A, P = 428, 2
 
     def __init__(self, state_dict, device='cuda:0', dtype=torch.float32):
-        sd = {k: torch.as_tensor(v).float() for k, v in state_dict.items()}
+        sd = {k: torch.as_tensor(v).to(_wide(dtype)) for k, v in state_dict.items()}
         self.n_mach = 2 if 'first_layer_mach1.weight' in sd else 1
         self.version = 9 + self.n_mach
         t = {}
@@ -1228,8 +1234,8 @@ class BotanikV1x(_TorchNet):
                     pi = pi + F.linear(y.flatten(1), t['pi' + k + 'W'], t['pi' + k + 'b'])
                 else:
                     v = v + F.linear(y.flatten(1), t['v' + k + 'W'], t['v' + k + 'b'])
-        logits = F.linear(F.relu(F.linear(pi, t['f1.W'], t['f1.b'])), t['f2.W'], t['f2.b']).float()
-        v = torch.tanh(F.linear(F.relu(F.linear(v, t['fv1.W'], t['fv1.b'])), t['fv2.W'], t['fv2.b']).float())
+        logits = F.linear(F.relu(F.linear(pi, t['f1.W'], t['f1.b'])), t['f2.W'], t['f2.b']).to(_wide(self.dtype))
+        v = torch.tanh(F.linear(F.relu(F.linear(v, t['fv1.W'], t['fv1.b'])), t['fv2.W'], t['fv2.b']).to(_wide(self.dtype)))
         logits = torch.where(valids.bool(), logits, torch.full_like(logits, -1e8))
         return torch.softmax(logits, dim=1).contiguous(), v.contiguous()
 

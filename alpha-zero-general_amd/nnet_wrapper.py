@@ -37,6 +37,7 @@ def _engine(hip, base, num_players=True):
     def make(sd, game, device, max_batch):
         kw = dict(num_players=game.P) if num_players else {}
         return hip(base(sd, device=device, **kw), max_batch=max_batch)
+    make.base, make.takes_num_players = base, bool(num_players)        # (read by the tests that evaluate the folded net on its own)
     return make
 
 
@@ -45,6 +46,8 @@ def _splendor_v80(sd, game, device, max_batch):
         return _nn.SplendorV80Hip(sd, num_players=2, device=device, max_batch=max_batch)
     return _nn.MobileNet1dHip(_nn.SplendorV80(sd, num_players=game.P, device=device), max_batch=max_batch)
 
+
+_splendor_v80.base, _splendor_v80.takes_num_players = _nn.SplendorV80, True
 
 EngineNet = collections.namedtuple('EngineNet', 'game variants version module evaluator')
 # the engine nets: game id, game variants (None = any), nn_version, trainable module (azg_amd.train) and the factory of its engine-kernel
