@@ -43,7 +43,7 @@ EXPORTS = [
     'azg_nn_mb1d_forward', 'azg_nn_mb1d_forward_h2', 'azg_nn_conv5_forward', 'azg_nn_conv5_forward_split', 'azg_nn_conv5_forward_h2', 'azg_nn_s78_forward', 'azg_nn_s78_forward_split', 'azg_nn_s78_forward_h2',
     'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62', 'azg_pick_actions', 'azg_env_playouts',
     'azg_eval_losses', 'azg_train_sample_ids', 'azg_train_gather', 'azg_train_losses',
-    'azg_train_adamw', 'azg_train_step_advance', 'azg_examples_expand',
+    'azg_train_adamw', 'azg_train_step_advance', 'azg_examples_expand', 'azg_train_gather_forms',
 ]
 
 
@@ -125,6 +125,8 @@ def lib():
         L.azg_train_step_advance.argtypes = [vp, vp]
     if hasattr(L, 'azg_examples_expand'):                   # (absent from older builds loaded through AZG_LIB for A/B runs)
         L.azg_examples_expand.argtypes = [i, i, vp, vp, vp, vp, vp, i, vp, vp, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, u64, u64, vp]
+    if hasattr(L, 'azg_train_gather_forms'):                # (absent from older builds loaded through AZG_LIB for A/B runs)
+        L.azg_train_gather_forms.argtypes = [i, i, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, vp, vp, u64, vp]
     if hasattr(L, 'azg_debug_rng_u01'):                    # (test aid, include/azg_testaids.h)
         L.azg_debug_rng_u01.argtypes = [u64, u64, u64, i, i, vp, vp]
     L.azg_stream_create_xcd.argtypes = [i, i, C.POINTER(vp)]

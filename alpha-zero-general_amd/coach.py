@@ -61,7 +61,11 @@ class Coach:
         device_history (None = args.device_history, default False): rank 0 keeps the example history on the GPU (history.DeviceHistory):
         an iteration's records are expanded into it in place (azg_examples_expand) and the trainer reads it in place, without a shuffle
         -- the wrapper must train with nn_args['device_batches'].  args.examples_file then names the file saveTrainExamples writes:
-        'reference' (checkpoint.examples, the default), 'columns' (checkpoint.examples.npz) or 'none'"""
+        'reference' (checkpoint.examples, the default), 'columns' (checkpoint.examples.npz) or 'none'.
+        device_history='compact': history.CompactHistory instead -- the records are kept, not their symmetric forms, and the trainer's
+        gather computes the rows of a batch (azg_train_gather_forms): the same rows, the same weights, 1 / forms-per-record of the memory.
+        args.examples_file may then also be 'records' (checkpoint.records.npz, the only file a compact history resumes from);
+        'reference' and 'columns' are written by materialising one iteration at a time"""
         self.game, self.args, self.log = game, args, log
         if not hasattr(nnet, 'save_checkpoint'):                     # a bare torch module: give it the NeuralNet surface
             engine_module = is_engine_module(nnet)
@@ -96,14 +100,20 @@ class Coach:
         self._sym_stream = 0
         self.results = []
         self.device_history = None
-        if bool(_get(args, 'device_history', False) if device_history is None else device_history):
+        kind = _get(args, 'device_history', False) if device_history is None else device_history
+        if isinstance(kind, str) and kind != 'compact':
+            raise ValueError("device_history must be False, True or 'compact', got %r" % (kind,))
+        self._compact = kind == 'compact'
+        if bool(kind):
             if not _get(getattr(self.nnet, 'args', None) or {}, 'device_batches', False):
-                raise ValueError("Coach(device_history=True) needs a wrapper that trains with nn_args['device_batches']: the host trainer "
-                                 "draws its batches from another random stream, and the device history is never shuffled")
-            if _get(args, 'examples_file', 'reference') not in ('reference', 'columns', 'none'):
-                raise ValueError("args.examples_file must be 'reference', 'columns' or 'none', got %r" % (_get(args, 'examples_file', None),))
-            from .history import DeviceHistory
-            self.device_history = DeviceHistory(game.S, game.A, game.P, device=game.device)
+                raise ValueError("Coach(device_history=%r) needs a wrapper that trains with nn_args['device_batches']: the host trainer "
+                                 "draws its batches from another random stream, and the device history is never shuffled" % (kind,))
+            files = ('reference', 'columns', 'none') + (('records',) if self._compact else ())
+            if _get(args, 'examples_file', 'reference') not in files:
+                raise ValueError("args.examples_file must be %s or %r, got %r" % (', '.join(repr(f) for f in files[:-1]), files[-1],
+                                                                                    _get(args, 'examples_file', None)))
+            from .history import CompactHistory, DeviceHistory
+            self.device_history = (CompactHistory if self._compact else DeviceHistory)(game.S, game.A, game.P, device=game.device)
             self._ref_iters = []                 # per iteration of the device history: its deque in the reference's layout, or None
 
     # engine-side aliases kept from round 1
@@ -234,7 +244,9 @@ class Coach:
         self._ref_iters.append(None)
         alpha = float(_get(self.args, 'dirichletAlpha', 0) or 0)
         if kept and alpha > 0:                                                 # Coach.py:169-176
-            avg_valid_moves = float(h.iteration_columns(-1)[3].sum(dtype=torch.int64).item()) / kept
+            # (a compact history sums the valids of the iteration's rows a chunk at a time: the same integer)
+            n_valid = h.iteration_valid_moves(-1) if self._compact else h.iteration_columns(-1)[3].sum(dtype=torch.int64).item()
+            avg_valid_moves = float(n_valid) / kept
             if not (1 / 1.5 < alpha / (10 / avg_valid_moves) < 1.5):
                 self.log('There are about %.1f valid moves per state, so I advise to set dirichlet to %.1f instead' % (avg_valid_moves, 10 / avg_valid_moves))
         return kept, total
@@ -308,7 +320,9 @@ class Coach:
             if lead and self.device_history is not None:
                 # the device sampler draws without replacement from the whole set: row order carries no meaning, nothing is shuffled
                 n_examples = self.device_history.n
-                self.nnet.train(self.device_history.columns(), log=self.log, seed=None if seed is None else int(seed) + it)
+                # (a compact history goes to the trainer as it is: its gather computes the rows of every batch)
+                self.nnet.train(self.device_history if self._compact else self.device_history.columns(), log=self.log,
+                                seed=None if seed is None else int(seed) + it)
             elif lead:
                 train_examples = [e for h in self.trainExamplesHistory for e in h]
                 (random.Random(int(seed) * 1000003 + it) if seed is not None else random).shuffle(train_examples)     # :185
@@ -387,6 +401,8 @@ class Coach:
             formats.save_train_examples(os.path.join(folder, 'checkpoint.examples'), self._ref_iters)
         elif _get(self.args, 'examples_file', 'reference') == 'columns':
             self.device_history.save_columns(os.path.join(folder, 'checkpoint.examples.npz'))
+        elif _get(self.args, 'examples_file', 'reference') == 'records':
+            self.device_history.save_records(os.path.join(folder, 'checkpoint.records.npz'))
         # engine-side state next to the reference's file: where the random streams of a resumed run continue (the reference draws
         # fresh OS randomness on every start; a seeded engine would replay iteration 1's boards, chance outcomes and noise)
         with open(os.path.join(folder, 'azg_state.json'), 'w') as f:
@@ -434,7 +450,13 @@ class Coach:
         else checkpoint.examples (this engine's or the reference's); the same azg_state.json, numItersHistory and maxlenOfQueue handling"""
         from .history import DeviceHistory
         n_hist, maxlen = int(_get(self.args, 'numItersHistory', 5)), int(_get(self.args, 'maxlenOfQueue', 10 ** 6))
-        if _get(self.args, 'examples_file', 'reference') == 'columns' and os.path.isfile(path + '.npz'):
+        if self._compact:
+            loaded = self._load_compact_history(path, n_hist, maxlen)
+            if loaded is None:
+                return
+            h, n_loaded = loaded
+            refs = [None] * len(h)
+        elif _get(self.args, 'examples_file', 'reference') == 'columns' and os.path.isfile(path + '.npz'):
             h = DeviceHistory.load_columns(path + '.npz', device=self.game.device)
             if h.widths != self.device_history.widths:
                 raise ValueError('%s.npz holds columns of widths %r, this game has %r' % (path, h.widths, self.device_history.widths))
@@ -472,6 +494,31 @@ class Coach:
             self._sym_stream = int(st.get('sym_stream', 0))
         else:                                                            # a history written by the reference: start behind it
             self.n_selfplay_waves = self.iter_base = n_loaded
+
+    def _load_compact_history(self, path, n_hist, maxlen):
+        """checkpoint.records.npz next to `path` -> (a CompactHistory trimmed as the default path trims, the iterations in the file), or
+        None when there is no file.  A file of expanded rows is refused: rows are not records, and nothing turns them back into records"""
+        from .history import CompactHistory
+        rec = os.path.join(os.path.dirname(path), 'checkpoint.records.npz')
+        if not os.path.isfile(rec):
+            for other in (path, path + '.npz'):
+                if os.path.isfile(other):
+                    raise ValueError("%s holds expanded example rows; a compact history (device_history='compact') keeps records and resumes "
+                                     "from checkpoint.records.npz only (args.examples_file = 'records'): load it with device_history=True" % other)
+            self.log('File "%s" with trainExamples not found!' % rec)
+            return None
+        h = CompactHistory.load_records(rec, device=self.game.device)
+        if h.widths != self.device_history.widths:
+            raise ValueError('%s holds records of widths %r, this game has %r' % (rec, h.widths, self.device_history.widths))
+        if h.rng_seed is not None and (h.game_id, h.variant, h.rng_seed) != (self.game.GAME_ID, self.game.variant, int(self.game.rng_seed)):
+            raise ValueError('%s was written for game (%d, %d) with rng_seed %d; this game is (%d, %d) with rng_seed %d: its rows would change'
+                             % (rec, h.game_id, h.variant, h.rng_seed, self.game.GAME_ID, self.game.variant, int(self.game.rng_seed)))
+        n_loaded = len(h)
+        while len(h) > n_hist:                                                                        # :254-256
+            h.pop_oldest()
+        for j in range(len(h)):                                                                       # :257-261 (drops from the END)
+            h.truncate_iteration(j, maxlen)
+        return h, n_loaded
 
     def temp_for_game(self, n):                                                                    # :273-276
         t_begin, t_end, half_life = 0.5, 0.0, abs(float(_get(self.args, 'tempThreshold', 10)))

@@ -139,4 +139,134 @@ __global__ __launch_bounds__(64) void k_examples_expand_built(const int8_t* stat
     if (lane_id() == 0) out_count[g] = k;
 }
 
+// ---- the other half: a training batch straight from the RECORDS (azg_train_gather_forms) -----------------------------------------------
+// Nothing forces the rows above to be stored: row r of the expanded history is a function of (record, form index) -- and of the record's
+// stream where the game draws.  One wave per BATCH row b: r = ids[b]; the record is the lowest g with row_end[g] > r (row_end is
+// non-decreasing: a wave-uniform binary search over read-only memory), the form is k = r - first_row[g], and row b of the outputs gets
+// the bytes k_examples_expand* writes to row first_row[g] + k -- the same candidates in the same order through the same interfaces.
+// An id that no record owns, or a k outside [0, NSYM_CAND), returns before anything but the index columns is read.
+struct FormsIn {
+    const int8_t* states; const float* pi; const float* z; const uint8_t* valids; const float* q;     // records [n][S | A | P | A | P]
+    const int64_t* first_row; const int64_t* row_end; const uint64_t* streams; int n;
+};
+struct FormsOut {
+    int8_t* boards; float* pi; float* z; uint8_t* valids; float* q;      // row-major [B][S | A | P | A | P]
+    int wide;                                                             // boards 4-byte aligned: dword stores where S % 4 == 0
+};
+
+// -> the record that owns virtual row ids[b] and (k) its form index; -1 when there is none
+__device__ __forceinline__ int forms_locate(const FormsIn& in, const int32_t* ids, int b, int ncand, int& k) {
+    const int64_t r = ids[b];
+    if (r < 0) return -1;
+    int lo = 0, hi = in.n;                                               // lowest g with row_end[g] > r
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (in.row_end[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= in.n) return -1;
+    const int64_t kk = r - in.first_row[lo];
+    if (kk < 0 || kk >= ncand) return -1;
+    k = (int)kk;
+    return lo;
+}
+
+// pi / valids of batch row b through the action map `src_of`, and the record's z / q
+template <class G, class F>
+__device__ __forceinline__ void forms_store_tail(const FormsIn& in, const FormsOut& o, int g, int b, F src_of) {
+    const float* pin = in.pi + (size_t)g * G::A;
+    const uint8_t* vin = in.valids + (size_t)g * G::A;
+    for (int a = lane_id(); a < G::A; a += 64) {
+        const int src = src_of(a);                                       // < 0: no action maps onto a
+        o.pi[(size_t)b * G::A + a] = src >= 0 ? pin[src] : 0.f;
+        o.valids[(size_t)b * G::A + a] = src >= 0 ? (uint8_t)(vin[src] != 0) : (uint8_t)0;
+    }
+    if (lane_id() < G::P) {
+        o.z[(size_t)b * G::P + lane_id()] = in.z[(size_t)g * G::P + lane_id()];
+        o.q[(size_t)b * G::P + lane_id()] = in.q[(size_t)g * G::P + lane_id()];
+    }
+}
+
+// Map games: form k is the k-th candidate with sym_exists; the candidates are counted 64 at a time, one per lane (Azul has 120).
+template <class G>
+__global__ __launch_bounds__(64) void k_gather_forms(FormsIn in, const int32_t* ids, int B, FormsOut o) {
+    __shared__ __attribute__((aligned(16))) int8_t st[G::SP];
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    int k = 0;
+    const int g = forms_locate(in, ids, b, G::NSYM_CAND, k);
+    if (g < 0) return;
+    Forest<G>::load_state_unpadded(st, in.states + (size_t)g * G::S);
+    int c = -1;
+    for (int c0 = 0; c0 < G::NSYM_CAND; c0 += 64) {
+        const int mine = c0 + lane_id();
+        const bool e = mine < G::NSYM_CAND && G::sym_exists(st, mine);
+        const uint64_t m = __ballot(e);
+        const int cnt = __popcll(m);
+        if (k < cnt) {                                                   // the lane whose candidate has k existing ones in front of it
+            const uint64_t hit = __ballot(e && __popcll(m & ((1ull << lane_id()) - 1ull)) == k);
+            c = c0 + (__ffsll((unsigned long long)hit) - 1);
+            break;
+        }
+        k -= cnt;
+    }
+    if (c < 0) return;                                                   // the record has fewer than k + 1 forms
+    if (G::S % 4 == 0 && o.wide) {
+        uint32_t* dst = (uint32_t*)(o.boards + (size_t)b * G::S);
+        for (int i = lane_id(); i < G::S / 4; i += 64) dst[i] = examples_state_dword<G>(st, c, 4 * i);
+    } else {
+        for (int i = lane_id(); i < G::S; i += 64) o.boards[(size_t)b * G::S + i] = G::sym_state_byte(st, c, i);
+    }
+    forms_store_tail<G>(in, o, g, b, [&](int a) { return G::sym_action_src(st, c, a); });
+}
+
+// Built games: the wave rebuilds candidates 0, 1, ... on the record's stream (rng_seed, streams[g]), counter from 0, exactly as
+// k_examples_expand_built does -- the draws of a dropped candidate included -- and stops at the k-th kept form.
+template <class G>
+__global__ __launch_bounds__(64) void k_gather_forms_built(FormsIn in, const int32_t* ids, int B, FormsOut o, uint64_t rng_seed) {
+    constexpr int NKEEP = G::SYM_DEDUP ? G::NSYM_CAND : 1;
+    __shared__ __attribute__((aligned(16))) int8_t st[G::SP];
+    __shared__ __attribute__((aligned(16))) int8_t kept[NKEEP][G::SP];
+    __shared__ int16_t act_src[G::A];
+    __shared__ int exists_s;
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    int want = 0;
+    const int g = forms_locate(in, ids, b, G::NSYM_CAND, want);
+    if (g < 0) return;
+    Forest<G>::load_state_unpadded(st, in.states + (size_t)g * G::S);
+    const uint8_t* vin = in.valids + (size_t)g * G::A;
+    Rng rng{rng_seed, in.streams ? in.streams[g] : (uint64_t)g, 0};
+    int k = 0;
+    for (int c = 0; c < G::NSYM_CAND; c++) {
+        int8_t* cand = kept[G::SYM_DEDUP ? (k < NKEEP ? k : NKEEP - 1) : 0];
+        for (int i = lane_id(); i < G::S; i += 64) cand[i] = st[i];
+        __syncthreads();
+        if (lane_id() == 0) exists_s = G::sym_build(st, c, cand, act_src, rng, vin) ? 1 : 0;
+        __syncthreads();
+        bool keep = exists_s != 0;
+        if (keep && G::SYM_DEDUP) {
+            for (int e = 0; e < k && keep; e++) {
+                bool diff = false;
+                for (int i = lane_id(); i < G::S; i += 64) diff |= kept[e][i] != cand[i];
+                keep = __ballot(diff) != 0;
+            }
+        }
+        if (keep) {
+            if (k == want) {
+                if (G::S % 4 == 0 && o.wide) {                           // (cand is 16-byte aligned: G::SP is a multiple of 16)
+                    uint32_t* dst = (uint32_t*)(o.boards + (size_t)b * G::S);
+                    const uint32_t* cw = (const uint32_t*)cand;
+                    for (int i = lane_id(); i < G::S / 4; i += 64) dst[i] = cw[i];
+                } else {
+                    for (int i = lane_id(); i < G::S; i += 64) o.boards[(size_t)b * G::S + i] = cand[i];
+                }
+                forms_store_tail<G>(in, o, g, b, [&](int a) { return (int)act_src[a]; });
+                return;
+            }
+            k++;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace azg

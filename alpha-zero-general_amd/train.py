@@ -520,6 +520,34 @@ def gather_batch(cols, ids, out=None):
     return tuple(out)
 
 
+def gather_forms(game_id, variant, records, first_row, row_end, streams, ids, rng_seed, out=None):
+    """azg_train_gather_forms: the batch rows `ids` (int32[B], CUDA) of the VIRTUAL rows that the n records = (boards int8[n, S], pi
+    f32[n, A], z f32[n, P], valids u8[n, A], q f32[n, P]) expand to -- form k of record g is virtual row first_row[g] + k, its live rows end
+    at row_end[g] (int64[n], non-decreasing), its forms draw from stream (rng_seed, streams[g]) (int64 / uint64 bits [n], or None = g) --
+    computed in one launch, without the expanded rows ever being stored (history.CompactHistory.gather) -> the five batch tensors of
+    gather_batch.  An id that no record owns gives an undefined row.  out: five tensors to fill instead of new ones."""
+    from . import _lib
+    boards, pi, z, valids, q = records
+    n, S = boards.shape
+    A, P, B = pi.shape[1], z.shape[1], ids.shape[0]
+    for x, dt, shape in ((boards, torch.int8, (n, S)), (pi, torch.float32, (n, A)), (z, torch.float32, (n, P)), (valids, torch.uint8, (n, A)),
+                         (q, torch.float32, (n, P)), (first_row, torch.int64, (n,)), (row_end, torch.int64, (n,)), (ids, torch.int32, (B,))):
+        assert x.is_cuda and x.dtype == dt and tuple(x.shape) == shape and x.is_contiguous() and x.device == boards.device, \
+            'gather_forms: dtype / shape / layout of an argument'
+    assert streams is None or (streams.is_cuda and streams.dtype in (torch.int64, torch.uint64) and tuple(streams.shape) == (n,) and
+                               streams.is_contiguous() and streams.device == boards.device), 'gather_forms: streams'
+    if out is None:
+        out = tuple(torch.empty((B, x.shape[1]), dtype=x.dtype, device=x.device) for x in records)
+    for o, x in zip(out, records):
+        assert o.dtype == x.dtype and tuple(o.shape) == (B, x.shape[1]) and o.is_contiguous() and o.device == x.device, \
+            'gather_forms: dtype / shape / layout of an output'
+    with torch.cuda.device(boards.device):
+        _lib.check(_lib.lib().azg_train_gather_forms(int(game_id), int(variant), _ptr(boards), _ptr(pi), _ptr(z), _ptr(valids), _ptr(q),
+                                                     _ptr(first_row), _ptr(row_end), None if streams is None else _ptr(streams), n, _ptr(ids), B,
+                                                     *[_ptr(o) for o in out], int(rng_seed) & (2 ** 64 - 1), _stream()))
+    return tuple(out)
+
+
 def train_losses(log_pi, v, target_pi, z, q, q_weight, v_coeff=0.25, out=None):
     """azg_train_losses on contiguous f32 CUDA tensors (log_pi / target_pi [B, A], v / z / q [B, P]) -> (grad_log_pi f32[B, A], grad_v
     f32[B, P], rows f64[B, 2], out f64[2]): the row sums and the totals (loss_pi, loss_v) of include/azg.h, and the gradient of loss_pi +
@@ -706,7 +734,9 @@ class DeviceAdamW:
 
 def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=0.5, device='cuda:0', seed=None, log=None, board_shape=None,
           device_batches=False, batch_ids=None, device_optimizer=False, graph_step=False, info=None, on_step=None):
-    """examples = (boards int8[n,S], pi f32[n,A], z f32[n,P], valids u8/bool[n,A], q f32[n,P]) tensors or arrays.
+    """examples = (boards int8[n,S], pi f32[n,A], z f32[n,P], valids u8/bool[n,A], q f32[n,P]) tensors or arrays -- or, with
+    device_batches=True, a history.CompactHistory: n is then its number of virtual rows and every batch is computed from its records
+    (azg_train_gather_forms); sampling, batch_ids, losses, optimiser and graph capture are the same.
     board_shape: give it for a module that expects the reference's inputs (float boards of getBoardSize(), bool valids:
     GenericNNetWrapper.py:60-63) instead of the engine modules' flat int8 boards.
     on_step(epoch, i_batch, step): called after every optimiser + scheduler step (step = i_batch + steps_per_epoch * epoch) -- the hook of
@@ -734,6 +764,9 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
     if device_batches:
         return _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_weight, device, seed, log, board_shape, on_step, batch_ids,
                                      device_optimizer, bool(graph_step), info if isinstance(info, dict) else None)
+    if _is_compact(examples):
+        raise ValueError('train: a CompactHistory holds records, not rows; only device_batches=True reads it (its gather computes the rows of '
+                         'a batch on the GPU)')
     boards, pi, z, valids, q = [torch.as_tensor(np.asarray(x.cpu()) if hasattr(x, 'cpu') else x).to(device) for x in examples[:5]]
     n = boards.shape[0]
     valids = valids.bool()
@@ -774,6 +807,11 @@ def train(module, examples, learn_rate=3e-3, batch_size=512, epochs=2, q_weight=
     return hist
 
 
+def _is_compact(examples):
+    from .history import CompactHistory
+    return isinstance(examples, CompactHistory)
+
+
 def _check_batch_ids(batch_ids, steps, batch_size):
     """-> int64 CPU tensor [steps, batch_size]"""
     ids = torch.as_tensor(np.asarray(batch_ids.cpu()) if hasattr(batch_ids, 'cpu') else np.asarray(batch_ids))
@@ -793,11 +831,18 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
     if torch.device(device).type != 'cuda':
         raise ValueError('train: device_batches=True needs a CUDA device, got %r (there is no CPU form of the batch kernels)' % (device,))
     dev = torch.device(device)
-    boards, pi, z, valids, q = [x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in examples[:5]]
-    n = int(boards.shape[0])
-    cols = (boards.to(dev).reshape(n, -1).to(torch.int8).contiguous(), pi.to(dev).reshape(n, -1).to(torch.float32).contiguous(),
-            z.to(dev).reshape(n, -1).to(torch.float32).contiguous(), (valids.to(dev).reshape(n, -1) != 0).view(torch.uint8).contiguous(),
-            q.to(dev).reshape(n, -1).to(torch.float32).contiguous())
+    if _is_compact(examples):                                                # the records stay what they are: n counts the VIRTUAL rows and
+        if examples.device != dev:                                           # history.gather computes the rows a batch names
+            raise ValueError('train: the CompactHistory lives on %s, the training runs on %s' % (examples.device, dev))
+        cols, n = examples, int(examples.n)
+        gather = examples.gather
+    else:
+        boards, pi, z, valids, q = [x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x)) for x in examples[:5]]
+        n = int(boards.shape[0])
+        cols = (boards.to(dev).reshape(n, -1).to(torch.int8).contiguous(), pi.to(dev).reshape(n, -1).to(torch.float32).contiguous(),
+                z.to(dev).reshape(n, -1).to(torch.float32).contiguous(), (valids.to(dev).reshape(n, -1) != 0).view(torch.uint8).contiguous(),
+                q.to(dev).reshape(n, -1).to(torch.float32).contiguous())
+        gather = lambda ids, out=None: gather_batch(cols, ids, out=out)      # noqa: E731
     steps_per_epoch = n // batch_size
     if steps_per_epoch == 0:
         raise ValueError('fewer examples (%d) than batch_size (%d)' % (n, batch_size))
@@ -819,7 +864,8 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
         if graph_step:
             if batch_ids is None:                                            # every epoch's ids before the capture: row s of epoch e is
                 ids_all = sample_ids(n, batch_size, epochs * steps_per_epoch, rng_seed, 0, device=dev)   # stream e * steps_per_epoch + s
-            hist = _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info)
+            hist = _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info,
+                                      gather)
             module.eval()
             return hist
         for ep in range(epochs):
@@ -829,7 +875,7 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
                 ids_ep = sample_ids(n, batch_size, steps_per_epoch, rng_seed, ep * steps_per_epoch, device=dev)
             losses = torch.empty((steps_per_epoch, 2), dtype=torch.float64, device=dev)
             for i_batch in range(steps_per_epoch):
-                b_boards, b_pi, b_z, b_valids, b_q = gather_batch(cols, ids_ep[i_batch])
+                b_boards, b_pi, b_z, b_valids, b_q = gather(ids_ep[i_batch])
                 if board_shape is not None:
                     b_boards = b_boards.reshape((batch_size,) + tuple(board_shape)).to(torch.float32)
                 if sched is None:
@@ -851,20 +897,23 @@ def _train_device_batches(module, examples, learn_rate, batch_size, epochs, q_we
     return hist
 
 
-def _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info):
+def _train_graph_steps(module, cols, ids_all, opt, batch_size, epochs, steps_per_epoch, q_weight, board_shape, on_step, log, info, gather=None):
     """The steps of train(graph_step=True), the current device being the columns': ids_all int32[total_steps, batch] on the device, opt a
-    DeviceAdamW.  The step body reads no host value that changes: its row of ids_all and its row of the loss buffer are picked by a device
+    DeviceAdamW.  cols: the five columns, or a CompactHistory with gather = its gather (the batch rows are then computed, not copied).  The step body reads no host value that changes: its row of ids_all and its row of the loss buffer are picked by a device
     index made from opt.step_counter with torch ops, and the optimiser takes its scalars by the same counter.  Everything is enqueued on
     one stream, so the captured graph is one linear chain."""
-    dev = cols[0].device
+    if gather is None:
+        gather = lambda ids, out=None: gather_batch(cols, ids, out=out)      # noqa: E731
+    rec = cols.record_columns() if _is_compact(cols) else cols               # (the widths and dtypes of a batch are the records')
+    dev = rec[0].device
     total = epochs * steps_per_epoch
     losses = torch.zeros((total, 2), dtype=torch.float64, device=dev)
     loss2 = torch.zeros(2, dtype=torch.float64, device=dev)
-    outs = tuple(torch.empty((batch_size, x.shape[1]), dtype=x.dtype, device=dev) for x in cols)
+    outs = tuple(torch.empty((batch_size, x.shape[1]), dtype=x.dtype, device=dev) for x in rec)
 
     def body():
         idx = opt.step_counter.clamp(0, total - 1)                           # int64[1]: this step's number
-        gather_batch(cols, ids_all.index_select(0, idx)[0], out=outs)
+        gather(ids_all.index_select(0, idx)[0], out=outs)
         b_boards = outs[0]
         if board_shape is not None:
             b_boards = b_boards.reshape((batch_size,) + tuple(board_shape)).to(torch.float32)

@@ -236,6 +236,28 @@ int azg_examples_expand(int game, int variant,
                         int8_t* out_states_dev, float* out_pi_dev, float* out_z_dev, uint8_t* out_valids_dev, float* out_q_dev,
                         int32_t* out_count_dev,         /* int32[n]: forms of group g, in both modes */
                         uint64_t rng_seed, uint64_t stream0, void* stream);
+/* The other half of the call above: a training batch computed from the RECORDS, so that the expanded rows need not be stored (one
+   wavefront per batch row, one launch).  The n records are the five columns [n][S | A | P | A | P]; three index columns place their
+   forms on an axis of VIRTUAL rows: form k of record g is virtual row first_row_dev[g] + k, the record's live rows end at row_end_dev[g]
+   (exclusive; NON-DECREASING in g -- a record with no live row repeats its predecessor's value), and its forms draw from the RNG
+   contract's stream (rng_seed, streams_dev[g]), counter from 0 (streams_dev == NULL: stream g).
+   For batch row b: r = ids_dev[b]; g = the lowest record with row_end_dev[g] > r (binary search); k = r - first_row_dev[g]; row b of the
+   five outputs (laid out as azg_train_gather's) then holds exactly the bytes azg_examples_expand writes to row first_row[g] + k when a
+   group expands that record on that stream: the same candidates in the same order (identity first), for the built games the same draws
+   and the same duplicate dropping -- at most the game's maximum number of forms is rebuilt per batch row.  z and q are the record's own;
+   valids are written as 0 / 1 bytes (valids != 0, as azg_train_gather writes them).
+   An id that no record owns (r < 0, r >= row_end_dev[n - 1]) or a k outside the record's forms cannot be refused without reading the
+   ids back: the row's content is then undefined (no memory outside the columns is touched).  An unknown game / variant, B < 0, n < 1
+   with B > 0 or a NULL pointer other than streams_dev (with B > 0) is an error and launches nothing; B == 0 launches nothing.  No
+   synchronisation and no allocation: the call can be captured in a graph. */
+int azg_train_gather_forms(int game, int variant,
+                           const int8_t* states_dev, const float* pi_dev, const float* z_dev, const uint8_t* valids_dev, const float* q_dev,
+                           const int64_t* first_row_dev,   /* int64[n]: virtual row of form 0 of record g (may lie below its first live row) */
+                           const int64_t* row_end_dev,     /* int64[n]: one past the last live virtual row of record g; non-decreasing */
+                           const uint64_t* streams_dev,    /* uint64[n] or NULL (= g) */
+                           int n, const int32_t* ids_dev, int B,
+                           int8_t* out_boards_dev, float* out_pi_dev, float* out_z_dev, uint8_t* out_valids_dev, float* out_q_dev,
+                           uint64_t rng_seed, void* stream);
 
 /* ---- forest: T independent MCTS trees, one wavefront per tree ----------------------------------------------------
    Replaces MCTS (MCTS.py:19-261) for a batch of trees and, in self-play mode, Coach.executeEpisode (Coach.py:37-84). */

@@ -13,7 +13,14 @@ are compared before anything is timed.  Each expansion's torch.cuda.max_memory_a
 
     python tools/time_history.py [--records-splendor 8192] [--records-azul 1024] [--history 5] [--repeat 3] [--out FILE.md]
 
-Every timing ends in a device synchronise; (b) is the median of --repeat runs, (a) runs once (it is host loops over every row)."""
+Every timing ends in a device synchronise; (b) is the median of --repeat runs, (a) runs once (it is host loops over every row).
+
+    python tools/time_history.py --compact [--records-splendor 32768] [--records-azul 4096] [--records-tlp 8192] [--batch 512] [--out FILE.md]
+
+The compact history (history.CompactHistory) against the device history on the same records, alternating in one process: append_records
+wall time (the compact one has no write pass), live device bytes (from the shapes, checked against device_bytes()), and the kernel time
+of one batch -- azg_train_gather_forms on the records against azg_train_gather on the expanded rows, the same ids, each as 20 launches
+captured in one graph and replayed (no host between the launches).  The rows of both are compared before anything is timed."""
 import argparse
 import json
 import os
@@ -155,10 +162,81 @@ def markdown(results):
     return '\n'.join(out)
 
 
+def graph_us(fn, calls=20, replays=20):
+    """device time of one fn() in microseconds: `calls` of them captured in one graph, the graph replayed `replays` times between two events"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(calls):
+            fn()
+    graph.replay()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(replays):
+        graph.replay()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e3 / (calls * replays)
+
+
+def measure_compact(name, g, n_records, repeat, batch):
+    from azg_amd import train
+    from azg_amd.history import CompactHistory, DeviceHistory
+    recs = synthetic_records(g, n_records)
+    s0 = 1 << 42
+    small = [t[:64].contiguous() for t in recs]
+    DeviceHistory(g.S, g.A, g.P, device=g.device).append_records(g, small, stream0=s0)                # warm-up: code objects, allocator
+    probe = CompactHistory(g.S, g.A, g.P, device=g.device)
+    rows, _ = probe.append_records(g, recs, stream0=s0)
+    del probe
+    t_dev, t_cmp = [], []
+    for _ in range(repeat):                                                                           # alternating, buffers allocated before
+        d = DeviceHistory(g.S, g.A, g.P, device=g.device, capacity=rows)
+        t_dev.append(timed(lambda: d.append_records(g, recs, stream0=s0))[0])
+        c = CompactHistory(g.S, g.A, g.P, device=g.device, capacity=n_records)
+        t_cmp.append(timed(lambda: c.append_records(g, recs, stream0=s0))[0])
+    assert d.n == c.n == rows
+    gen = torch.Generator(device='cpu').manual_seed(3)
+    check = torch.randint(0, rows, (4096,), generator=gen).to(torch.int32).to(g.device)
+    cols = d.columns()
+    assert same_rows(c.gather(check), [x[check.long()] for x in cols]), 'the compact history gives other rows'
+    row_bytes = g.S + 4 * g.A + g.A + 8 * g.P
+    assert c.device_bytes() == n_records * (row_bytes + 24) and sum(x.numel() * x.element_size() for x in cols) == rows * row_bytes
+    ids = torch.randint(0, rows, (batch,), generator=gen).to(torch.int32).to(g.device)
+    outs = train.gather_batch(cols, ids)
+    k_exp, k_cmp = [], []
+    for _ in range(2):                                                                                # alternating
+        k_exp.append(graph_us(lambda: train.gather_batch(cols, ids, out=outs)))
+        k_cmp.append(graph_us(lambda: c.gather(ids, out=outs)))
+    return dict(game=name, records=n_records, rows=rows, forms_per_record=rows / n_records, batch=batch, append_device_s=t_dev, append_compact_s=t_cmp,
+                gather_us=k_exp, gather_forms_us=k_cmp, bytes_device=rows * row_bytes, bytes_compact=c.device_bytes(), row_bytes=row_bytes)
+
+
+def markdown_compact(results):
+    out = ['| game | records | rows | forms / record | device history MiB | compact history MiB | `DeviceHistory.append_records` (s), per run | '
+           '`CompactHistory.append_records` (s), per run | `azg_train_gather`, B = %d (µs), per run | `azg_train_gather_forms`, B = %d (µs), per run | d = difference of the medians (µs) |'
+           % (results[0]['batch'], results[0]['batch']), '|---|---|---|---|---|---|---|---|---|---|---|']
+    fmt = lambda xs, f: ' / '.join(f % x for x in xs)  # noqa: E731
+    for r in results:
+        out.append('| %s | %d | %d | %.1f | %.1f | %.1f | %s | %s | %s | %s | %.1f |' % (
+            r['game'], r['records'], r['rows'], r['forms_per_record'], r['bytes_device'] / 2 ** 20, r['bytes_compact'] / 2 ** 20,
+            fmt(r['append_device_s'], '%.4f'), fmt(r['append_compact_s'], '%.4f'), fmt(r['gather_us'], '%.1f'), fmt(r['gather_forms_us'], '%.1f'),
+            statistics.median(r['gather_forms_us']) - statistics.median(r['gather_us'])))
+    return '\n'.join(out)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--records-splendor', type=int, default=8192)
-    ap.add_argument('--records-azul', type=int, default=1024)
+    ap.add_argument('--compact', action='store_true', help='the compact history against the device history (see above)')
+    ap.add_argument('--records-splendor', type=int, default=None, help='default 8192; 32768 with --compact')
+    ap.add_argument('--records-azul', type=int, default=None, help='default 1024; 4096 with --compact')
+    ap.add_argument('--records-tlp', type=int, default=8192, help='The Little Prince, 3 players (--compact only)')
+    ap.add_argument('--batch', type=int, default=512, help='rows of the timed batch (--compact only)')
     ap.add_argument('--history', type=int, default=5, help='numItersHistory of the long case')
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--out', default=None, help='write the markdown table and the JSON lines here as well')
@@ -167,6 +245,23 @@ def main():
         raise SystemExit('time_history.py measures on the GPU: no device found')
     from azg_amd import games
     results = []
+    if a.compact:
+        for name, make, n in (('Splendor-2p', lambda: games.SplendorGame(2), 32768 if a.records_splendor is None else a.records_splendor),
+                              ('Azul', games.AzulGame, 4096 if a.records_azul is None else a.records_azul),
+                              ('The Little Prince 3p', lambda: games.TLPGame(num_players=3), a.records_tlp)):
+            if n > 0:
+                results.append(measure_compact(name, make(), n, a.repeat, a.batch))
+                print(json.dumps(results[-1]), flush=True)
+                torch.cuda.empty_cache()
+        text = markdown_compact(results)
+        print(text)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write(text + '\n\n' + '\n'.join(json.dumps(r) for r in results) + '\n')
+        return
+    a.records_splendor = 8192 if a.records_splendor is None else a.records_splendor
+    a.records_azul = 1024 if a.records_azul is None else a.records_azul
     for name, g, n in (('Splendor-2p', games.SplendorGame(2), a.records_splendor), ('Azul', games.AzulGame(), a.records_azul)):
         if n > 0:
             results.append(measure(name, g, n, a.history, a.repeat))

@@ -7,7 +7,11 @@ The Splendor-2p SplendorV80Module on n synthetic examples.  Per n and per path t
 figure is wall time per step with everything a path makes the host do.  The paths alternate, `--repeats` rounds per size.  Separately: the
 kernel time of the batch launches by device events (sample_ids for one epoch of n // batch steps; gather and losses for one batch), of the
 optimiser's two launches on the V80 parameter set against torch's AdamW step on the same set, and the CPU time of one torch.randperm(n),
-which the legacy path pays per step.  Prints a markdown report (and writes it to --out)."""
+which the legacy path pays per step.  Prints a markdown report (and writes it to --out).
+    python tools/time_train_step.py --compact [--compact-records 32768] [--batch 512] [--repeats 2] [--out FILE.md]
+The graph_step path alone on one Splendor-2p history (the synthetic records of tools/time_history.py), read as expanded rows
+(history.DeviceHistory.columns(), the path before the compact history) and as records (history.CompactHistory), alternating; with the
+kernel time of the two gathers on the same batch (20 launches captured in one graph, replayed)."""
 import argparse
 import os
 import sys
@@ -43,7 +47,7 @@ PATHS = (('legacy', dict()), ('device_batches', dict(device_batches=True)),
 def time_path(ex, batch, warmup, steps, switches):
     import torch
     from azg_amd import train
-    n = ex[0].shape[0]
+    n = ex.n if hasattr(ex, 'n_records') else ex[0].shape[0]
     spe = n // batch
     epochs = -(-(warmup + steps) // spe)
     mark = {}
@@ -81,6 +85,53 @@ def event_ms(fn, reps=200, warm=20):
     return a.elapsed_time(b) / reps
 
 
+def compact_report(args):
+    """--compact: graph_step on expanded rows against graph_step on records, one history"""
+    import statistics
+    import torch
+    from azg_amd import games, train
+    from azg_amd.history import CompactHistory, DeviceHistory
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    from time_history import graph_us, synthetic_records
+    g = games.SplendorGame(2)
+    recs = synthetic_records(g, args.compact_records)
+    d, c = DeviceHistory(g.S, g.A, g.P, device=g.device), CompactHistory(g.S, g.A, g.P, device=g.device)
+    assert d.append_records(g, recs, stream0=1 << 42) == c.append_records(g, recs, stream0=1 << 42)
+    cols = d.columns()
+    runs = {'expanded': [], 'compact': []}
+    for _ in range(args.repeats):
+        runs['expanded'].append(time_path(cols, args.batch, args.warmup, args.steps, dict(device_batches=True, graph_step=True)))
+        runs['compact'].append(time_path(c, args.batch, args.warmup, args.steps, dict(device_batches=True, graph_step=True)))
+    ids = torch.randint(0, d.n, (args.batch,), generator=torch.Generator(device='cpu').manual_seed(3)).to(torch.int32).to(g.device)
+    outs = train.gather_batch(cols, ids)
+    k_exp, k_cmp = [], []
+    for _ in range(2):
+        k_exp.append(graph_us(lambda: train.gather_batch(cols, ids, out=outs)))
+        k_cmp.append(graph_us(lambda: c.gather(ids, out=outs)))
+    dk = (statistics.median(k_cmp) - statistics.median(k_exp)) / 1e3
+    spread = max(runs['expanded']) - min(runs['expanded'])
+    fmt = lambda xs, f='%.3f': ' / '.join(f % x for x in xs)  # noqa: E731
+    bound = statistics.median(runs['expanded']) + max(dk, 0.0) + spread
+    lines = ['# `graph_step` on a compact history against the expanded rows (`tools/time_train_step.py --compact`)', '',
+             '%s, torch %s.  SplendorV80Module (2 players), batch %d, %d warm-up + %d timed steps per run, alternating in one process.'
+             % (torch.cuda.get_device_name(0), torch.__version__, args.batch, args.warmup, args.steps),
+             'Splendor-2p: %d records, %d rows; %.1f MiB as expanded rows, %.1f MiB as records.'
+             % (c.n_records, c.n, d.n * c.row_bytes / 2 ** 20, c.device_bytes() / 2 ** 20), '',
+             '| | expanded rows | compact |', '|---|---|---|',
+             '| `graph_step` step (ms), per run | %s | %s |' % (fmt(runs['expanded']), fmt(runs['compact'])),
+             '| gather kernel, B = %d (µs), per run | %s | %s |' % (args.batch, fmt(k_exp, '%.1f'), fmt(k_cmp, '%.1f')), '',
+             'd (kernel-time difference of the medians) = %.4f ms, s (spread of the expanded runs) = %.4f ms: the compact step is accepted up to'
+             % (dk, spread),
+             'median(expanded) + d + s = %.4f ms; its median is %.4f ms -- %s.'
+             % (bound, statistics.median(runs['compact']), 'within' if statistics.median(runs['compact']) <= bound else 'ABOVE the bound')]
+    text = '\n'.join(lines) + '\n'
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument('--out', default=None)
@@ -89,11 +140,15 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=50)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--repeats', type=int, default=2, help='alternating rounds of the four paths per size')
+    ap.add_argument('--compact', action='store_true', help='graph_step on a CompactHistory against the expanded rows (see above)')
+    ap.add_argument('--compact-records', type=int, default=32768, help='Splendor-2p records of the --compact history')
     args = ap.parse_args(argv)
     import torch
     from azg_amd import train
     if not torch.cuda.is_available():
         raise SystemExit('time_train_step: needs a GPU (a CPU timing says nothing about it)')
+    if args.compact:
+        return compact_report(args)
     dev = 'cuda:0'
     lines = ['# Training step: legacy, `device_batches`, `device_optimizer`, `graph_step` (`tools/time_train_step.py`)', '',
              '%s, torch %s.  SplendorV80Module (2 players), batch %d, %d warm-up + %d timed optimiser steps per run, the four paths in one'
