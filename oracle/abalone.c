@@ -1,5 +1,7 @@
 /* ORACLE (test infrastructure).  Abalone env step: a scalar restatement of abalone/AbaloneLogicNumba.py (Board :166-440),
- * INITIAL_LAYOUT = 1 (Belgian Daisy), ENABLE_DYNAMIC_KOMI = False (the shipped constants, :5-6).
+ * for every value of its two module constants (:5-6).  g->variant is the C-ABI variant of include/azg.h: bits 0-1 the layout
+ * (1 Belgian Daisy -- the shipped INITIAL_LAYOUT --, 2 German Daisy, 3 classic), 4 = ENABLE_DYNAMIC_KOMI (shipped False): misc[0][3]
+ * then says whether player 0 wins a score tie at the round limit, and an odd swap_players flips it.
  *
  * State = int8 [9][9][4] (axial grid; plane 0 my marbles, 1 opponent's, 2 board mask (4 <= r + q <= 12), 3 misc with
  * misc[0][0..2] = score of player 0, score of player 1, move counter); byte index = (r*9 + q)*4 + plane.
@@ -102,8 +104,8 @@ int abalone_make_move(const azo_game* g, int8_t* s, int move, int player, int64_
     return 1 - player;
 }
 
-void abalone_game_ended(const azo_game* g, const int8_t* s, int next_player, float* out) {                     /* :398-413 */
-    (void)g; (void)next_player;
+void abalone_game_ended(const azo_game* g, const int8_t* s, int next_player, float* out) {                     /* :376-392 */
+    (void)next_player;
     const int s0 = CELL(s, 0, 0, 3), s1 = CELL(s, 0, 1, 3);
     out[0] = out[1] = 0.f;
     if (s0 >= 6) { out[0] = 1.f; out[1] = -1.f; return; }
@@ -111,32 +113,39 @@ void abalone_game_ended(const azo_game* g, const int8_t* s, int next_player, flo
     if (CELL(s, 0, 2, 3) >= 127) {
         if (s0 > s1) { out[0] = 1.f; out[1] = -1.f; }
         else if (s1 > s0) { out[0] = -1.f; out[1] = 1.f; }
+        else if (g->variant & 4) { out[0] = CELL(s, 0, 3, 3) == 1 ? 1.f : -1.f; out[1] = -out[0]; }                 /* :385-389 */
         else { out[0] = out[1] = 0.001f; }
     }
 }
 
-void abalone_swap_players(const azo_game* g, int8_t* s, int k) {                                               /* :415-426 */
-    (void)g;
+void abalone_swap_players(const azo_game* g, int8_t* s, int k) {                                               /* :394-406 */
     if (k % 2 != 1) return;
     for (int c = 0; c < 81; c++) { const int8_t t = s[4 * c]; s[4 * c] = s[4 * c + 1]; s[4 * c + 1] = t; }
     const int8_t t = CELL(s, 0, 0, 3); CELL(s, 0, 0, 3) = CELL(s, 0, 1, 3); CELL(s, 0, 1, 3) = t;
+    if (g->variant & 4) CELL(s, 0, 3, 3) = (int8_t)(1 - CELL(s, 0, 3, 3));
 }
 
 int abalone_get_round(const azo_game* g, const int8_t* s) { (void)g; return CELL(s, 0, 2, 3); }
 int abalone_get_score(const azo_game* g, const int8_t* s, int p) { (void)g; return p == 0 ? CELL(s, 0, 0, 3) : CELL(s, 0, 1, 3); }
 
-void abalone_init_board(const azo_game* g, int8_t* s, azo_rng* rng) {                                          /* :175-222, layout 1 */
-    (void)rng;
+void abalone_init_board(const azo_game* g, int8_t* s, azo_rng* rng) {                                          /* :167-233 */
     memset(s, 0, (size_t)g->S);
     for (int r = 0; r < 9; r++)
         for (int q = 0; q < 9; q++)
             if (r + q >= 4 && r + q <= 12) CELL(s, r, q, 2) = 1;
-    static const int opp_rows[6][3] = {{0, 4, 6}, {1, 3, 6}, {2, 3, 5}, {6, 4, 6}, {7, 3, 6}, {8, 3, 5}};
-    static const int my_rows[6][3] = {{0, 7, 9}, {1, 6, 9}, {2, 6, 8}, {6, 1, 3}, {7, 0, 3}, {8, 0, 2}};
+    /* {row, q_lo, q_hi} of the opponent's and of player 0's marbles: classic :179-187, Belgian Daisy :189-207, German Daisy :209-227 */
+    static const int opp_rows[3][6][3] = {{{0, 4, 9}, {1, 3, 9}, {2, 4, 7}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}},
+                                          {{0, 4, 6}, {1, 3, 6}, {2, 3, 5}, {6, 4, 6}, {7, 3, 6}, {8, 3, 5}},
+                                          {{1, 4, 6}, {2, 3, 6}, {3, 3, 5}, {5, 4, 6}, {6, 3, 6}, {7, 3, 5}}};
+    static const int my_rows[3][6][3] = {{{8, 0, 5}, {7, 0, 6}, {6, 2, 5}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}},
+                                         {{0, 7, 9}, {1, 6, 9}, {2, 6, 8}, {6, 1, 3}, {7, 0, 3}, {8, 0, 2}},
+                                         {{1, 6, 8}, {2, 5, 8}, {3, 5, 7}, {5, 2, 4}, {6, 1, 4}, {7, 1, 3}}};
+    const int layout = (g->variant & 3) == 3 ? 0 : (g->variant & 3);                /* the reference's INITIAL_LAYOUT */
     for (int i = 0; i < 6; i++) {
-        for (int q = opp_rows[i][1]; q < opp_rows[i][2]; q++) CELL(s, opp_rows[i][0], q, 1) = 1;
-        for (int q = my_rows[i][1]; q < my_rows[i][2]; q++) CELL(s, my_rows[i][0], q, 0) = 1;
+        for (int q = opp_rows[layout][i][1]; q < opp_rows[layout][i][2]; q++) CELL(s, opp_rows[layout][i][0], q, 1) = 1;
+        for (int q = my_rows[layout][i][1]; q < my_rows[layout][i][2]; q++) CELL(s, my_rows[layout][i][0], q, 0) = 1;
     }
+    if (g->variant & 4) CELL(s, 0, 3, 3) = (int8_t)(int)(2.0 * azo_rng_u01(rng));   /* np.random.randint(2) :233 */
 }
 
 /* the symmetry `rot` (0..5 clockwise 60-degree turns) after `flip` of one cell (:112-121, 431-438) */

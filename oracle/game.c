@@ -113,7 +113,9 @@ int azo_game_init(azo_game* g, int game_id, int variant) {
         return 0;
     }
     if (game_id == AZO_ABALONE) {
-        g->variant = 1;                      /* INITIAL_LAYOUT = 1 (Belgian Daisy), no dynamic komi */
+        const int v = variant ? variant : 1; /* bits 0-1: 1 Belgian Daisy (the shipped INITIAL_LAYOUT), 2 German Daisy, 3 classic; 4: dynamic komi */
+        if (v < 1 || v > 7 || (v & 3) == 0) return -1;
+        g->variant = v;
         g->P = 2;
         g->rows = 81; g->cols = 4;           /* observation_size (9, 9, 4), AbaloneLogicNumba.py:46-48 */
         g->S = 324;
@@ -285,7 +287,7 @@ void azo_known_start(const azo_game* g, int8_t* s, int a, int b) {
     else if (g->id == AZO_AKROPOLIS) { azo_rng r; memset(&r, 0, sizeof(r)); akropolis_init_board(g, s, &r); }
     else if (g->id == AZO_BOTANIK) { azo_rng r; memset(&r, 0, sizeof(r)); botanik_init_board(g, s, &r); }
     else if (g->id == AZO_TLP) { azo_rng r; memset(&r, 0, sizeof(r)); tlp_init_board(g, s, &r); }                      /* first market from stream (0,0) */
-    else if (g->id == AZO_ABALONE) abalone_init_board(g, s, NULL);
+    else if (g->id == AZO_ABALONE) { azo_rng r; memset(&r, 0, sizeof(r)); abalone_init_board(g, s, &r); }
     else if (g->id == AZO_MINIVILLES) { azo_rng r; memset(&r, 0, sizeof(r)); minivilles_init_board(g, s, &r); }   /* first dice from stream (0,0) */
     else if (g->id == AZO_SPLENDOR) splendor_known_start(g, s);
     else if (g->id == AZO_AZUL) azul_known_start(g, s);
