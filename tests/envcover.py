@@ -11,7 +11,11 @@ The recipe of rows(): game g starts from og.getInitBoard(og.rng(seed=99, stream=
 ply, with probability 0.7 (np.random.default_rng(1)) the action is uniform among the valid ids that no earlier row of this run took, if
 there is one, otherwise uniform among all valid ids -- but a valid id that the variant's env_*.npz fixture takes and this run has not
 yet taken goes first, so that the run covers what the old fixture covers; random_seed = MAGIC_SEEDS[(g + ply) % 8] (the eight seeds of MCTS.py:14 -- the
-oracle is pinned to the reference's seeded draws for these only); the game stops at getGameEnded(...).any()."""
+oracle is pinned to the reference's seeded draws for these only); the game stops at getGameEnded(...).any().
+
+Two further families (tests/test_env_coverage_drawing.py, tests/test_gpu_env_coverage_drawing.py), each described where it is defined:
+DRAWING, the games whose step draws whatever random_seed says (rows_drawing, take_drawing: a counter stream per game, selected rows
+re-evaluated on the stream of their place in a launch), and rows_six / select_six, Abalone games steered to a win by six marbles."""
 import os
 
 import numpy as np
@@ -37,7 +41,7 @@ DTYPES = dict(state=np.int8, player=np.int8, valid=np.uint8, action=np.int16, se
 
 def oracle_game(variant):
     import azg_oracle as O
-    name, v = VARIANTS[variant]
+    name, v = VARIANTS[variant] if variant in VARIANTS else DRAWING[variant]
     if name == 'ABALONE':
         from azg_amd.games import abalone_variant
         v = abalone_variant(*v)[2]
@@ -57,6 +61,8 @@ _cache = {}
 def rows(variant, games=None):
     """every transition of `games` steered oracle games (None: GAMES, else 400): dict of state int8[n, S], player, valid (np.packbits
     rows), action, seed, next_state, next_player, ended f32[n, P], game, ply.  take() adds score, round and canonical form."""
+    if variant in DRAWING:
+        return rows_drawing(variant, games)
     games = GAMES.get(variant, 400) if games is None else games
     if (variant, games) in _cache:
         return _cache[variant, games]
@@ -117,6 +123,8 @@ def select(r, cap=16384, spaced=None):
     4  other rows, evenly spaced, until `cap` rows are selected (`spaced`: at most that many of them -- for the slow live reference)."""
     n, A = len(r['action']), r['A']
     _, g1 = np.unique(r['action'], return_index=True)
+    if 'n_uniforms' in r:                                    # the games that always draw: both the drawing and the non-drawing path of an id
+        g1 = np.union1d(g1, np.unique(r['action'].astype(np.int64) * 256 + r['n_uniforms'], return_index=True)[1])
     g1 = np.sort(g1)
     seen = unpack(r['valid'][g1], A).any(axis=0)
     fv = first_valid(r)
@@ -133,6 +141,8 @@ def select(r, cap=16384, spaced=None):
 
 def take(r, idx):
     """the rows idx of every field of rows(), plus what the oracle says of their next_state: score int16[n, P], round, canonical"""
+    if r['variant'] in DRAWING:
+        return take_drawing(r, idx)
     out = {k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in r.items()}
     og = oracle_game(r['variant'])
     ns, npl = out['next_state'], out['next_player']
@@ -186,3 +196,233 @@ def oracle_outputs(variant, d):
         out['score'].append([og.getScore(nb, q) for q in range(og.P)]); out['round'].append(og.getRound(nb))
         out['canonical'].append(og.getCanonicalForm(nb, npl).reshape(-1))
     return {k: np.array(v, dtype=DTYPES[k]) for k, v in out.items()}
+
+
+# ---- the games that always draw: Botanik (deck), Minivilles (dice, purple cards), The Little Prince (market refill) ----------------
+# Their step consumes uniforms whatever random_seed says (tests/test_env_coverage_drawing.py checks), so game g is played on the
+# stream og.rng(seed=INIT_SEED, stream=g): getInitBoard consumes from it and every step continues it.  A launch of the C-ABI gives
+# row j the stream stream0 + j, so a row cannot keep its game's stream: take() re-evaluates the selected row j on
+# og.rng(seed=COVER_SEED, stream=j) at the counter the row had in its game, and that is what reference, fixture and kernels are held to.
+DRAWING = {'botanik': ('BOTANIK', 0), 'minivilles2': ('MINIVILLES', 2), 'minivilles3': ('MINIVILLES', 3), 'minivilles4': ('MINIVILLES', 4),
+           'tlp3': ('TLP', 3), 'tlp4': ('TLP', 4), 'tlp5': ('TLP', 5)}
+COVER_SEED = 2718
+# Botanik does not saturate under the plain rule (ids taken 230 / 285 / 305 after 200 / 1000 / 1600 games), and a game is about 80 rows
+# of 2310 bytes: its run is bounded, steered with a one-ply lookahead, and keeps states only for the rows take() is asked for (replayed)
+DRAWING_GAMES = {'botanik': 1000}
+LOOKAHEAD_CANDIDATES = 3
+DTYPES.update(counter=np.int64, n_uniforms=np.int8, counter_after=np.int64, eject=np.bool_)
+
+
+def _copy_rng(rng):
+    return type(rng).from_buffer_copy(rng)
+
+
+def _botanik_lookahead(og, board, player, idx, taken, rng, pick):
+    """one ply ahead, for the plies at which the plain rule has no untaken id to offer: among (at most LOOKAHEAD_CANDIDATES of) the moves
+    that can free a card or place one (ids >= 15), uniform among those whose successor has a valid id the run has not taken; else, with
+    probability 0.5 each where there is one, a move that fills a register (ids < 15: a card is freed only from a filled register) or one
+    that grows a machine (35..426, not the throw-away 427); else None: the plain rule's uniform choice"""
+    far = idx[idx >= 15]
+    if len(far) > LOOKAHEAD_CANDIDATES:
+        far = far[np.sort(np.argsort([pick.random() for _ in far], kind='stable')[:LOOKAHEAD_CANDIDATES])]
+    good = []
+    for a in far:
+        nb, npl = og.getNextState(board, player, int(a), 0, _copy_rng(rng))
+        if (og.getValidMoves(nb, npl) & ~taken).any():
+            good.append(int(a))
+    if good:
+        return good[int(pick.random() * len(good))]
+    for cand in (idx[idx < 15], idx[(idx >= 35) & (idx < og.A - 1)]):
+        if len(cand) and pick.random() < 0.5:
+            return int(cand[int(pick.random() * len(cand))])
+    return None
+
+
+def rows_drawing(variant, games=None, lookahead=None):
+    """rows() for a variant of DRAWING: the same steering (probability 0.7 for an untaken id, what the old fixture takes first), game g on
+    the stream (INIT_SEED, g) from getInitBoard on; per row also `counter` (of that stream before the step) and `n_uniforms` (consumed by
+    the step).  `seed` is recorded as in rows() and changes nothing.  lookahead (None: Botanik only) adds _botanik_lookahead at the plies
+    where the plain rule would choose among all valid ids.  Botanik rows carry no state / next_state: states() replays them."""
+    games = DRAWING_GAMES.get(variant, 400) if games is None else games
+    lookahead = variant == 'botanik' if lookahead is None else lookahead
+    if (variant, games, lookahead) in _cache:
+        return _cache[variant, games, lookahead]
+    og = oracle_game(variant)
+    keep_states = variant != 'botanik'
+    pick = np.random.default_rng(1)
+    taken = np.zeros(og.A, dtype=bool)
+    wanted = np.zeros(og.A, dtype=bool)
+    wanted[np.unique(np.load(os.path.join(GOLDEN, fixture_name(variant)))['action'])] = True
+    keys = ('player', 'valid', 'action', 'seed', 'next_player', 'ended', 'game', 'ply', 'counter', 'n_uniforms')
+    rec = {k: [] for k in keys + (('state', 'next_state') if keep_states else ())}
+    for g in range(games):
+        rng = og.rng(seed=INIT_SEED, stream=g)
+        board, player = og.getInitBoard(rng), 0
+        for ply in range(MAX_PLIES):
+            valid = og.getValidMoves(board, player)
+            idx = np.flatnonzero(valid)
+            if not len(idx):
+                break
+            fresh = idx[~taken[idx]]
+            first = fresh[wanted[fresh]]
+            fresh = first if len(first) else (fresh if pick.random() < 0.7 else fresh[:0])
+            a = None
+            if lookahead and not len(fresh):
+                a = _botanik_lookahead(og, board, player, idx, taken, rng, pick)
+            if a is None:
+                cand = fresh if len(fresh) else idx
+                a = int(cand[int(pick.random() * len(cand))])
+            taken[a] = True
+            seed, counter = MAGIC_SEEDS[(g + ply) % 8], int(rng.counter)
+            nb, npl = og.getNextState(board, player, a, seed, rng)
+            ended = og.getGameEnded(nb, npl)
+            if keep_states:
+                rec['state'].append(board.reshape(-1)); rec['next_state'].append(nb.reshape(-1))
+            rec['player'].append(player); rec['valid'].append(np.packbits(valid)); rec['action'].append(a); rec['seed'].append(seed)
+            rec['next_player'].append(npl); rec['ended'].append(ended); rec['game'].append(g); rec['ply'].append(ply)
+            rec['counter'].append(counter); rec['n_uniforms'].append(int(rng.counter) - counter)
+            board, player = nb, npl
+            if ended.any():
+                break
+    out = {k: np.array(v, dtype=DTYPES[k]) for k, v in rec.items()}
+    out['A'], out['P'], out['variant'] = og.A, og.P, variant
+    _cache[variant, games, lookahead] = out
+    return out
+
+
+def states(r, idx):
+    """the states of the rows idx of a DRAWING run: stored, or (Botanik) the games of those rows played again from their actions"""
+    if 'state' in r:
+        return r['state'][idx]
+    og = oracle_game(r['variant'])
+    out = np.empty((len(idx), og.S), dtype=np.int8)
+    where = {int(i): j for j, i in enumerate(idx)}
+    start = np.flatnonzero(r['ply'] == 0)
+    for g in np.unique(r['game'][idx]):
+        lo = int(start[g])
+        hi = int(start[g + 1]) if g + 1 < len(start) else len(r['action'])
+        rng = og.rng(seed=INIT_SEED, stream=int(g))
+        board = og.getInitBoard(rng)
+        for i in range(lo, hi):
+            assert int(rng.counter) == r['counter'][i], (g, i)
+            if i in where:
+                out[where[i]] = board.reshape(-1)
+            board, _ = og.getNextState(board, int(r['player'][i]), int(r['action'][i]), 0, rng)
+    return out
+
+
+def take_drawing(r, idx):
+    """take() for a DRAWING run: the fields of the rows idx as played (state, player, valid, action, seed, counter, game, ply), and the
+    oracle's step of row j -- its position in idx -- on the stream (COVER_SEED, j) at that counter: next_state, next_player, ended,
+    score, round, canonical, n_uniforms, counter_after"""
+    og = oracle_game(r['variant'])
+    out = {k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in r.items() if k not in ('state', 'next_state')}
+    out['state'] = states(r, idx)
+    rec = {k: [] for k in ('next_state', 'next_player', 'ended', 'score', 'round', 'canonical', 'n_uniforms', 'counter_after')}
+    for j in range(len(idx)):
+        rng = og.rng(seed=COVER_SEED, stream=j)
+        rng.counter = int(out['counter'][j])
+        nb, npl = og.getNextState(out['state'][j].reshape(og.shape), int(out['player'][j]), int(out['action'][j]), int(out['seed'][j]), rng)
+        rec['next_state'].append(nb.reshape(-1)); rec['next_player'].append(npl); rec['ended'].append(og.getGameEnded(nb, npl))
+        rec['score'].append([og.getScore(nb, q) for q in range(og.P)]); rec['round'].append(og.getRound(nb))
+        rec['canonical'].append(og.getCanonicalForm(nb, npl).reshape(-1))
+        rec['n_uniforms'].append(int(rng.counter) - int(out['counter'][j])); rec['counter_after'].append(int(rng.counter))
+    out.update({k: np.array(v, dtype=DTYPES[k]).reshape((len(idx),) + np.shape(v[0]) if len(v) else (0,)) for k, v in rec.items()})
+    return out
+
+
+def oracle_outputs_drawing(variant, d, seed=None):
+    """the oracle on the rows of d (state, player, action, counter; seed: d's, or one value for every row) with row j on the stream
+    (COVER_SEED, j): the fields of oracle_outputs plus n_uniforms and counter_after"""
+    og = oracle_game(variant)
+    n = len(d['action'])
+    r = dict(state=d['state'], player=d['player'], action=d['action'], counter=d['counter'], variant=variant,
+             seed=d['seed'] if seed is None else np.full(n, seed, dtype=DTYPES['seed']))
+    out = take_drawing(r, np.arange(n))
+    out['valid'] = np.array([np.packbits(og.getValidMoves(d['state'][i].reshape(og.shape), int(d['player'][i]))) for i in range(n)],
+                            dtype=np.uint8).reshape(n, -1)
+    return out
+
+
+# ---- Abalone: games won by six marbles ------------------------------------------------------------------------------------------
+# No game of rows() ends by six (127 steered plies push too rarely), so the s0 >= 6 / s1 >= 6 branch of game_ended and the scores 5
+# and 6 need a run of their own, which leaves the rows of rows() where they are.
+SHOVE = 0.5
+SIX_GAMES = {'abalone': 200, 'abalone_german': 200, 'abalone_belgian_komi': 200, 'abalone_classic': 150, 'abalone_classic_komi': 150}
+
+
+def rows_six(variant, games=None):
+    """rows() steered towards pushes.  A valid move that raises the mover's score is an ejecting id: one that no earlier row of this
+    run took as an ejection goes first; otherwise, with probability 0.9, the action is uniform among the ejecting ids; otherwise, with
+    probability SHOVE where there is one, uniform among the moves that displace an opposing marble (that is what brings marbles to the
+    edge: without it the classic layout gave 4 wins by six in 200 games, under the floor of tests/test_env_coverage_drawing.py);
+    otherwise the rule of rows().  Seeded like rows(); the fields of rows() plus `eject` (the row's move raised the mover's score)."""
+    games = SIX_GAMES[variant] if games is None else games
+    if (variant, games, 'six') in _cache:
+        return _cache[variant, games, 'six']
+    og = oracle_game(variant)
+    pick = np.random.default_rng(1)
+    taken = np.zeros(og.A, dtype=bool)
+    ejected = np.zeros(og.A, dtype=bool)
+    wanted = np.zeros(og.A, dtype=bool)
+    wanted[np.unique(np.load(os.path.join(GOLDEN, fixture_name(variant)))['action'])] = True
+    rec = {k: [] for k in ('state', 'player', 'valid', 'action', 'seed', 'next_state', 'next_player', 'ended', 'game', 'ply', 'eject')}
+    for g in range(games):
+        board, player = og.getInitBoard(og.rng(seed=INIT_SEED, stream=g)), 0
+        for ply in range(MAX_PLIES):
+            valid = og.getValidMoves(board, player)
+            idx = np.flatnonzero(valid)
+            if not len(idx):
+                break
+            seed, before = MAGIC_SEEDS[(g + ply) % 8], og.getScore(board, player)
+            after = [og.getNextState(board, player, int(a), seed)[0] for a in idx]
+            push = idx[[og.getScore(b, player) > before for b in after]]
+            shove = idx[[(b[..., 1 - player] != board[..., 1 - player]).any() for b in after]]     # an opposing marble moved
+            new = push[~ejected[push]]
+            if len(new):
+                cand = new
+            elif len(push) and pick.random() < 0.9:
+                cand = push
+            elif len(shove) and pick.random() < SHOVE:
+                cand = shove
+            else:
+                fresh = idx[~taken[idx]]
+                first = fresh[wanted[fresh]]
+                fresh = first if len(first) else (fresh if pick.random() < 0.7 else fresh[:0])
+                cand = fresh if len(fresh) else idx
+            a = int(cand[int(pick.random() * len(cand))])
+            taken[a] = True
+            nb, npl = og.getNextState(board, player, a, seed)
+            eject = og.getScore(nb, player) > before
+            ejected[a] |= eject
+            ended = og.getGameEnded(nb, npl)
+            rec['state'].append(board.reshape(-1)); rec['player'].append(player); rec['valid'].append(np.packbits(valid))
+            rec['action'].append(a); rec['seed'].append(seed); rec['next_state'].append(nb.reshape(-1)); rec['next_player'].append(npl)
+            rec['ended'].append(ended); rec['game'].append(g); rec['ply'].append(ply); rec['eject'].append(eject)
+            board, player = nb, npl
+            if ended.any():
+                break
+    out = {k: np.array(v, dtype=DTYPES[k]) for k, v in rec.items()}
+    out['A'], out['P'], out['variant'] = og.A, og.P, variant
+    _cache[variant, games, 'six'] = out
+    return out
+
+
+def scores_after(r):
+    """int[n, P]: getScore of every player on the next_state of every row"""
+    og = oracle_game(r['variant'])
+    return np.array([[og.getScore(b, p) for p in range(og.P)] for b in r['next_state']], dtype=np.int64).reshape(len(r['action']), og.P)
+
+
+def select_six(r):
+    """-> (idx, group) of rows_six, without repeats, in row order inside a group: 1 the first row that takes each ejecting action id,
+    2 every row whose next state has a score of 5 or 6 for either player, 3 the last transition of every game"""
+    n = len(r['action'])
+    ej = np.flatnonzero(r['eject'])
+    g1 = np.sort(ej[np.unique(r['action'][ej], return_index=True)[1]])
+    g2 = np.setdiff1d(np.flatnonzero((scores_after(r) >= 5).any(axis=1)), g1)
+    last = np.flatnonzero(np.append(r['game'][1:] != r['game'][:-1], True)) if n else np.zeros(0, dtype=np.int64)
+    g3 = np.setdiff1d(last, np.concatenate([g1, g2]))
+    idx = np.concatenate([g1, g2, g3])
+    group = np.concatenate([np.full(len(x), k + 1, dtype=np.int8) for k, x in enumerate((g1, g2, g3))])
+    return idx, group
