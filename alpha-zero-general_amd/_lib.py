@@ -44,6 +44,7 @@ EXPORTS = [
     'azg_nn_aba21_forward', 'azg_nn_sw62_forward', 'azg_nn_akr31_forward', 'azg_nn_bot_forward', 'azg_forest_async_rounds_sw62', 'azg_pick_actions', 'azg_env_playouts',
     'azg_eval_losses', 'azg_train_sample_ids', 'azg_train_gather', 'azg_train_losses',
     'azg_train_adamw', 'azg_train_step_advance', 'azg_examples_expand', 'azg_train_gather_forms',
+    'azg_env_lookahead', 'azg_greedy_candidates',
 ]
 
 
@@ -114,6 +115,9 @@ def lib():
         L.azg_pick_actions.argtypes = [i, vp, vp, i, i, vp, u64, u64, vp, vp, vp]
     if hasattr(L, 'azg_env_playouts'):                      # (absent from older builds loaded through AZG_LIB for A/B runs)
         L.azg_env_playouts.argtypes = [i, i, vp, vp, vp, i, i, i, u64, u64, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, 'azg_env_lookahead'):                     # (absent from older builds loaded through AZG_LIB for A/B runs)
+        L.azg_env_lookahead.argtypes = [i, i, vp, vp, vp, i, i, u64, u64, vp, vp, vp, vp, vp, vp, vp]
+        L.azg_greedy_candidates.argtypes = [i, i, i, vp, vp, vp, i, vp, vp, vp]
     if hasattr(L, 'azg_eval_losses'):                       # (absent from older builds loaded through AZG_LIB for A/B runs)
         L.azg_eval_losses.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, C.c_float, vp, vp, vp, i, vp]
     if hasattr(L, 'azg_train_losses'):                      # (absent from older builds loaded through AZG_LIB for A/B runs)

@@ -15,14 +15,17 @@ with `azg_amd.mcts.MCTS`-based players already works unchanged (one game at a ti
 Baselines (pit.py's players, <G>Players.py): instead of an nnet a contestant may be a RandomContestant() -- <G>Players.RandomPlayer.play,
 uniform among the valid moves -- or a PolicyContestant(nnet) -- the net's policy without a search.  Neither owns a forest; their move
 is one launch of azg_pick_actions (csrc/pick.hip.h) on the [T, A] rows of the ply.  vs_random(...) is the pit-style call.
+GreedyContestant(rule) -- <G>Players.GreedyPlayer.play -- is a third baseline: a one-ply lookahead (csrc/lookahead.hip.h) narrows the valid
+moves to the rule's candidates before the same pick; vs_greedy(...) is `pit.py <game> greedy <checkpoint>`.
 nnet.RolloutEvaluator in the place of an nnet makes a contestant a pure MCTS (uniform prior, random playouts as the leaf value), and
 random_games(...) plays whole random games in one launch (csrc/playout.hip.h)."""
 import ctypes as C
 
 import torch
 
+from . import _lib
 from ._lib import check, lib
-from .games import _ptr, _stream
+from .games import GREEDY_RULES, _ptr, _stream, greedy_candidates
 from .mcts import BatchedMCTS
 
 PICK_UNIFORM, PICK_ARGMAX, PICK_SAMPLE = 0, 1, 2
@@ -56,6 +59,37 @@ class RandomContestant:
         return None, game.valid_moves_batch(canonical, None)
 
 
+class GreedyContestant:
+    """<G>Players.GreedyPlayer.play as an arena contestant: a one-ply lookahead.  Per ply: every successor of every board in one launch
+    (games.HipGame.lookahead_batch, csrc/lookahead.hip.h), the candidate moves of the rule (games.greedy_candidates), and the move uniform
+    among them -- the pick of RandomContestant with the candidates in the place of the valid moves: same kernel, same stream
+    stream0 + (c + 1) << 30 + i of game i, one draw per move.
+    rule='reference': the reference's player, quirks included (include/azg.h, azg_greedy_candidates) -- Splendor, Azul (from the board
+    alone: no lookahead) and Abalone; the reference's other six games define no greedy rule and raise.  rule='lead': this project's own
+    rule for any game, the moves after which the mover's score leads the best other seat's by most.
+    The lookahead of game i peeks at the env step's draws on a stream of its own, arena stream0 + 3 << 30 + i, always from counter 0
+    (it collides with neither the arena's env stream stream0 + i nor the two pick streams); like RandomContestant's, game i's moves are a
+    function of rng_seed and i, whatever n_parallel and however the match is dealt out."""
+    mode = PICK_UNIFORM
+    NO_RULE = 'azg_greedy_candidates: the reference defines no greedy player for this game'
+
+    def __init__(self, rule='reference'):
+        if rule not in GREEDY_RULES:
+            raise ValueError("GreedyContestant: rule is 'reference' or 'lead', not %r" % (rule,))
+        self.rule, self.peek_stream0 = rule, 3 * (1 << 30)
+
+    def begin_wave(self, arena_stream0, first_game_index):
+        self.peek_stream0 = arena_stream0 + 3 * (1 << 30) + first_game_index
+
+    def probs_valid(self, game, canonical):
+        if self.rule == 'reference' and game.GAME_ID not in (_lib.SPLENDOR, _lib.AZUL, _lib.ABALONE):
+            raise _lib.AzgError(self.NO_RULE)
+        if self.rule == 'reference' and game.GAME_ID == _lib.AZUL:
+            return None, greedy_candidates(game, self.rule, canonical, game.valid_moves_batch(canonical, None), None)
+        ahead = game.lookahead_batch(canonical, stream0=self.peek_stream0)
+        return None, greedy_candidates(game, self.rule, canonical, ahead.valid, ahead.scores)
+
+
 class PolicyContestant:
     """the raw policy of `nnet` as an arena contestant: one predict_batch per ply (all T rows of the wave: a fixed batch shape, rows of
     games where the contestant is not to move are ignored), then the first-index argmax over the valid moves, or with sample=True a move
@@ -82,7 +116,7 @@ class BatchedArena:
         self.temp_for_game = temp_for_game
         kw = [dict(rng_seed=int(getattr(game, 'rng_seed', 0)), stream0=stream0 + (c + 1) * (1 << 30) + first_game_index) for c in (0, 1)]
         # a contestant is a search (BatchedMCTS on its own forest) or a baseline object; self.mcts lists the searches only
-        self.contestants = [n if isinstance(n, (RandomContestant, PolicyContestant)) else
+        self.contestants = [n if isinstance(n, (RandomContestant, PolicyContestant, GreedyContestant)) else
                             BatchedMCTS(game, n, a, n_parallel, node_capacity=node_capacity, **kw[c])
                             for c, (n, a) in enumerate(((nnet1, args1), (nnet2, args2 if args2 is not None else args1)))]
         self.mcts = [m for m in self.contestants if isinstance(m, BatchedMCTS)]
@@ -106,6 +140,9 @@ class BatchedArena:
         # a baseline contestant draws game i's moves from a stream of its own, stream0 + (c + 1) << 30 + i, from counter 0: a function of the
         # game index only, whatever n_parallel and however the match is dealt out
         pick_counters = [None if isinstance(m, BatchedMCTS) else torch.zeros(T, dtype=torch.int64, device=dev) for m in self.contestants]
+        for m in self.contestants:                                           # (a lookahead contestant's peek stream follows the game index too)
+            if hasattr(m, 'begin_wave'):
+                m.begin_wave(self.stream0, first_game_index)
         for ply in range(self.max_plies):
             if bool(done.all().item()):
                 break
@@ -161,6 +198,14 @@ def vs_random(game, nnet, args, num, **kw):
     playGames -> (won, lost, draws) from the net's side.  kw: BatchedArena's (n_parallel defaults to min(num, 64))"""
     kw.setdefault('n_parallel', max(1, min(int(num), 64)))
     return BatchedArena(game, nnet, RandomContestant(), args, **kw).playGames(num)
+
+
+def vs_greedy(game, nnet, args, num, rule='reference', **kw):
+    """pit.py's second question of a net (`pit.py <game> greedy <checkpoint>`): `num` games of (nnet, args) with its search against
+    GreedyContestant(rule), seats alternating as in playGames -> (won, lost, draws) from the net's side.  kw: BatchedArena's (n_parallel
+    defaults to min(num, 64))"""
+    kw.setdefault('n_parallel', max(1, min(int(num), 64)))
+    return BatchedArena(game, nnet, GreedyContestant(rule), args, **kw).playGames(num)
 
 
 def random_games(game, num, stream0=0, max_plies=4096):

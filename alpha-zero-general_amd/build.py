@@ -20,6 +20,7 @@ UNITS = [('azg.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_async.hip', ['-mllvm', '-disable-promote-alloca-to-lds', '-mllvm', '-disable-machine-licm'] + os.environ.get('AZG_ASYNC_FLAGS', '').split()),
          ('azg_async_sel.hip', ['-mllvm', '-disable-promote-alloca-to-lds'] + os.environ.get('AZG_ASYNC_SEL_FLAGS', '').split()),
          ('azg_playout.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
+         ('azg_lookahead.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_loss.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_train.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
          ('azg_examples.hip', ['-mllvm', '-disable-promote-alloca-to-lds'])]
@@ -30,6 +31,7 @@ UNITS = [('azg.hip', ['-mllvm', '-disable-promote-alloca-to-lds']),
 # per descent), hence the two units.  AZG_ASYNC_FLAGS / AZG_ASYNC_SEL_FLAGS: further code-generation experiments.)
 # (azg_nn.hip also holds the per-CU round kernel, azg_fused.hip.h: 16 tree descents + their net forward in one workgroup)
 # (azg_playout.hip: the random-playout kernels, playout.hip.h -- a unit of its own so that they cannot change what is inlined into azg.hip's kernels)
+# (azg_lookahead.hip: the one-ply lookahead and greedy-candidate kernels, lookahead.hip.h -- a unit of its own for the same reason)
 # (azg_loss.hip: the validation-loss kernels, loss.hip.h -- a unit of its own for the same reason)
 # (azg_train.hip: the training step's batch kernels, train.hip.h -- draw, gather, losses + gradients; a unit of its own for the same reason)
 # (azg_examples.hip: the example-expansion kernels, examples.hip.h -- records to dense example rows; a unit of its own for the same reason)

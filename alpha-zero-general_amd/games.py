@@ -44,6 +44,43 @@ def playouts_into(game, boards, players, k, max_plies, active, stream0, counters
                                  _ptr(ended), _ptr(plies), _ptr(status), _ptr(out_boards), _ptr(out_players), _ptr(out_actions), _stream()))
 
 
+Lookahead = collections.namedtuple('Lookahead', 'valid scores ended next_player states')
+INT32_MIN = -2 ** 31
+GREEDY_RULES = {'reference': 0, 'lead': 1}                   # AZG_GREEDY_REFERENCE, AZG_GREEDY_LEAD (include/azg.h)
+
+
+def default_waves_per_state(A):
+    """waves of azg_env_lookahead per position when the caller names none.  Every wave of a position re-reads the state and rebuilds the
+    whole valid mask -- work that grows with A -- before it steps its share of the valid moves, so the rule follows A:
+        A <= 256          min(8, ceil(A / 8)): a wave per 8 ids, 8 for Splendor (81) and Santorini without gods (162), where the mask is
+                          cheap next to 35-49 steps per position -- within 3 % of the best of the sweep at 4096 positions, 4-7 times
+                          faster than one wave at 64;
+        256 < A <= 1024   4 (not measured: between the two);
+        A > 1024          2: every further wave re-does Abalone's mask over 3402 ids, which at 4096 positions costs more than sharing the
+                          64 steps saves -- one wave is best there and two cost 6 % more; at 64 positions two take 30 % less than one.
+    The sweep is in profiles/r17_lookahead.md.  The result never depends on the number."""
+    A = int(A)
+    return max(1, min(8, (A + 7) // 8)) if A <= 256 else 4 if A <= 1024 else 2
+
+
+def greedy_candidates(game, rule, canonical, valid, scores, active=None, out=None):
+    """azg_greedy_candidates (include/azg.h): the greedy players' candidate sets u8[n, A] for canonical boards int8[n, S] from what
+    lookahead_batch gave for them (valid u8[n, A], scores int32[n, A, P]; scores may be None for Azul's reference rule).  rule:
+    'reference' (the reference's GreedyPlayer: Splendor, Azul, Abalone) or 'lead' (the mover's lead after the move: any game).  Rows with
+    active == 0 keep what `out` (zeros when not given) holds."""
+    n = canonical.shape[0]
+    canonical = canonical.reshape(n, game.S)
+    if out is None:
+        out = torch.zeros((n, game.A), dtype=torch.uint8, device=canonical.device)
+    for x, dt, shape in ((canonical, (torch.int8,), (n, game.S)), (valid, (torch.uint8,), (n, game.A)), (scores, (torch.int32,), (n, game.A, game.P)),
+                         (active, (torch.uint8, torch.bool), (n,)), (out, (torch.uint8,), (n, game.A))):
+        assert x is None or (x.dtype in dt and tuple(x.shape) == shape and x.is_contiguous() and x.device == canonical.device), \
+            'greedy_candidates: dtype / shape / layout of an argument'
+    check(lib().azg_greedy_candidates(game.GAME_ID, game.variant, GREEDY_RULES[rule], _ptr(canonical), _ptr(valid), _ptr(scores), n, _ptr(active),
+                                      _ptr(out), _stream()))
+    return out
+
+
 class HipGame:
     GAME_ID = None
 
@@ -115,6 +152,30 @@ class HipGame:
         oa = torch.full((n, k, max_plies), -1, dtype=torch.int32, device=dev) if trace else None
         playouts_into(self, boards, players, k, max_plies, active, stream0, counters, ended, plies, status, ob, op, oa)
         return Playouts(ended, plies, status, ob, op, oa)
+
+    def lookahead_batch(self, boards, players=None, active=None, waves_per_state=None, stream0=0, counters=None, successor_states=False):
+        """all successors of n boards in one launch (azg_env_lookahead): for every valid action a of board t, what next_state_batch
+        (random_seed 0, stream stream0 + t, from counters[t]: int64[n], never written; None: from 0) and game_ended_batch give for it.
+        -> Lookahead(valid u8[n, A], scores i32[n, A, P], ended f32[n, A, P], next_player i32[n, A], states int8[n, A, S] with
+        successor_states else None), in the seat numbering of the input boards.  Rows of invalid actions, and every row of a board with
+        active == 0 (valid included), hold the fill values: scores INT32_MIN, ended 0, next_player -1, states 0, valid 0.
+        waves_per_state (1 .. 64; None: default_waves_per_state(A)) only deals the work out, the result does not depend on it."""
+        n, dev = boards.shape[0], self.device
+        boards = boards.reshape(n, self.S)
+        assert boards.dtype == torch.int8 and boards.is_contiguous()
+        for x, dt in ((players, (torch.int32,)), (active, (torch.uint8, torch.bool)), (counters, (torch.int64,))):
+            assert x is None or (x.dtype in dt and tuple(x.shape) == (n,) and x.is_contiguous() and x.device == boards.device), \
+                'lookahead: dtype / shape / layout of an argument'
+        W = default_waves_per_state(self.A) if waves_per_state is None else int(waves_per_state)
+        valid = torch.zeros((n, self.A), dtype=torch.uint8, device=dev)
+        scores = torch.full((n, self.A, self.P), INT32_MIN, dtype=torch.int32, device=dev)
+        ended = torch.zeros((n, self.A, self.P), dtype=torch.float32, device=dev)
+        nxt = torch.full((n, self.A), -1, dtype=torch.int32, device=dev)
+        states = torch.zeros((n, self.A, self.S), dtype=torch.int8, device=dev) if successor_states else None
+        check(lib().azg_env_lookahead(self.GAME_ID, self.variant, _ptr(boards), _ptr(players), _ptr(active), n, W,
+                                      C.c_uint64(int(self.rng_seed) & (2 ** 64 - 1)), C.c_uint64(int(stream0) & (2 ** 64 - 1)), _ptr(counters),
+                                      _ptr(valid), _ptr(scores), _ptr(ended), _ptr(nxt), _ptr(states), _stream()))
+        return Lookahead(valid, scores, ended, nxt, states)
 
     def max_symmetries(self):
         return {0: 10 + 2 * self.P, 1: 8, 2: 120, 3: 1, 4: 12, 5: 2 * self.P + 1, 6: 14, 7: 6, 8: 3}[self.GAME_ID]    # Splendor, Santorini, Azul, Minivilles, Abalone, TLP, Botanik, Akropolis, Smallworld

@@ -138,6 +138,57 @@ int azg_env_playouts(int game, int variant,
                      int32_t* out_actions_dev,      /* [n][k][max_plies] or NULL: the moves; entries past plies untouched */
                      void* stream);
 
+/* ---- one-ply lookahead: all successors of n positions, one launch (waves_per_state wavefronts per position) -----------
+   The loop of <G>Players.GreedyPlayer.play (splendor/SplendorPlayers.py:76-79, abalone/AbalonePlayers.py:195-201) -- for every valid
+   move, getNextState and getScore -- for n positions at once.  For state t:
+     out_valid_dev[t] = getValidMoves(board, player), as azg_env_valid_moves writes it;
+   and for every valid action a, row [t][a] of the other outputs is exactly what these two calls give:
+     azg_env_next_state on that row with action a and random_seed = 0, on the RNG contract's stream (rng_seed, stream0 + t) from
+       counters_dev[t] (NULL: from 0)                              -> out_states_dev[t][a] (optional), out_next_player_dev[t][a];
+     azg_env_game_ended(next state, next player)                   -> out_ended_dev[t][a], out_scores_dev[t][a] (getScore of all P seats).
+   Every candidate of a state starts from the SAME counter: the call is a peek.  counters_dev is never written and nothing is advanced.
+   SEAT FRAME: the input board's -- the env step never renumbers seats (Game.getNextState returns (player + 1) % P without a swap), as
+   in azg_env_playouts.  For a canonical board (the mover is seat 0) entry 0 of a row is the mover's.
+   Rows of invalid actions keep what the buffers held; so do ALL rows of a state with active == 0, out_valid_dev[t] included.
+   The work of a state is dealt out over waves_per_state wavefronts (the valid action of rank r goes to wave r mod waves_per_state); the
+   result does not depend on it.  n == 0 launches nothing.  An unknown game / variant, waves_per_state outside 1 .. 64 or a NULL required
+   output is an error and launches nothing.  No synchronisation and no allocation. */
+int azg_env_lookahead(int game, int variant,
+                      const int8_t* states_dev,       /* [n][S] */
+                      const int32_t* players_dev,     /* [n], NULL = player 0 everywhere */
+                      const uint8_t* active_dev,      /* [n], NULL = every state */
+                      int n, int waves_per_state,     /* 1 .. 64 */
+                      uint64_t rng_seed, uint64_t stream0,
+                      const uint64_t* counters_dev,   /* [n] or NULL (every peek from 0); never written */
+                      uint8_t* out_valid_dev,         /* [n][A] */
+                      int32_t* out_scores_dev,        /* [n][A][P] */
+                      float*   out_ended_dev,         /* [n][A][P] */
+                      int32_t* out_next_player_dev,   /* [n][A] */
+                      int8_t*  out_states_dev,        /* [n][A][S] or NULL: the successor boards */
+                      void* stream);
+
+/* ---- the greedy players' candidate sets (one wavefront per position) ---------------------------------------------------
+   canonical_states_dev int8[n][S] are CANONICAL boards (the mover is seat 0), valid_dev u8[n][A] and scores_dev i32[n][A][P] what
+   azg_env_lookahead wrote for them.  out_candidates_dev[t][a] = 1 where a is a move the player may take, else 0; a position without a
+   valid move gives an all-zero row; a position with active == 0 keeps its row.  The move itself is
+   azg_pick_actions(mode 0, probs NULL, valid = candidates): uniform among the candidates, one draw.
+   rule AZG_GREEDY_REFERENCE -- <G>Players.GreedyPlayer of the reference, quirks included; Splendor, Azul and Abalone only (any other
+   game: error "the reference defines no greedy player for this game"):
+     Splendor (splendor/SplendorPlayers.py:68-90): s_a = score of seat 1 after move a -- the reference reads seat 1 of a board that
+       getNextState did not renumber, i.e. the OPPONENT's score; M = max s_a over the valid moves; init = getScore(board, 0).  M != init:
+       the valid a with s_a == M.  Otherwise the valid ids in [0, 12); if none, those in [30, 60); if none, every valid id.
+     Abalone (abalone/AbalonePlayers.py:182-206): the valid a of maximal score[1] - score[0] after the move (same seat reading).
+     Azul (azul/AzulPlayers.py:36-70): no lookahead (scores_dev may be NULL), one candidate from the board alone: the first valid move of
+       maximal (to_line, -to_floor) with to_line = min(line + 1 - board[11][line], n), to_floor = n - to_line, n = board[3 + a / 30][colour]
+       (line 5: to_line = 0) -- except that the reference's `if not best_move` also replaces a kept move 0, so move 0 is the candidate
+       only when no other move is valid.
+   rule AZG_GREEDY_LEAD -- this project's own, any game: the valid a of maximal score[0] - max over p >= 1 of score[p] after the move
+     (the mover's lead; what the reference's players intend). */
+#define AZG_GREEDY_REFERENCE 0
+#define AZG_GREEDY_LEAD 1
+int azg_greedy_candidates(int game, int variant, int rule, const int8_t* canonical_states_dev, const uint8_t* valid_dev,
+                          const int32_t* scores_dev, int n, const uint8_t* active_dev, uint8_t* out_candidates_dev, void* stream);
+
 /* ---- validation losses on a net's outputs (one wavefront per example row) -------------------------------------------
    Replaces the loss half of GenericNNetWrapper.evaluate (:159-177; loss_pi / loss_v :179-190) for B examples: pi_dev f32[B][A] are
    PROBABILITIES as the engine nets return them, v_dev f32[B][P], target_pi_dev f32[B][A], z_dev / q_dev f32[B][P], active_dev u8[B]
