@@ -573,7 +573,10 @@ int azg_nn_v80_forward_split(const int8_t* boards_dev, const uint8_t* valid_dev,
    descale (HOST array of 16 floats) = 2^-k / 64 for W0, {We, W1, W2, Wp} x (trunk, policy, value), Wpi1, Wpi2, Wv1. */
 /* Activation range of the f16 x 2 ("h2") forwards -- azg_nn_v80_forward_h2, azg_nn_mb1d_forward_h2, azg_nn_conv5_forward_h2,
    azg_nn_s78_forward_h2: their LDS planes hold 64 * x as f16 (hi) + f16 (lo), so the 1e-5 contract holds for activations and
-   residual-stream values |x| < 1023 (the reference's trained nets stay below ~50).  Beyond that the value SATURATES: the kernels run
+   residual-stream values |x| < 1023.  The reference's trained nets, float64 modules on the boards of reachable positions
+   (tests/test_net_reachable_boards.py): The Little Prince 166 to 181 over its player counts (212 with 5 players on the early-game rows
+   of netfwd_tlp5_v83.npz), Abalone 71 to 113 over its layouts, Santorini V78 89, every other shipped net at most 71; the stand-in
+   weights of Minivilles 4p and Botanik reach 125 and 134.  Beyond the range the value SATURATES: the kernels run
    with the FP16_OVFL bit of the wave MODE register set, so an f16 conversion that overflows gives +-65504 instead of inf -- pi / v stay
    finite, never NaN (tests/test_nnet.py::test_h2_kernels_saturate_out_of_range_activations_gpu).  A net that may leave the range (e.g.
    a diverging training run) is evaluated with the f32-operand kernels (azg_nn_v80_forward / _mb1d_forward / _conv5_forward /

@@ -1,5 +1,6 @@
 """Weight sets for the engine nets other than the shipped checkpoints (a helper module of tests/test_net_weight_sets.py and
-tests/test_gpu_net_weight_sets.py, not a conftest).
+tests/test_gpu_net_weight_sets.py, not a conftest; tests/reachboards.py and its tests use the calibrated set, the float64 reference and
+the operand forms / evaluator factory at the end of this file).
 
 Every row of nnet_wrapper.ENGINE_NETS is held on two weight sets made from seeds at test time:
 
@@ -235,8 +236,8 @@ def float32_outputs(module, b, k):
     return pi.double(), v.double()
 
 
-def max_activation(module, b, k):
-    """the largest |output| of any submodule in the float64 forward"""
+def float64_outputs_and_max_activation(module, b, k, chunk=None):
+    """(exp(log_pi), v, the largest |output| of any submodule) of one float64 forward, `chunk` rows at a time (None: all at once)"""
     m = _double_copy(module)
     top = [0.0]
 
@@ -247,8 +248,14 @@ def max_activation(module, b, k):
     for sub in m.modules():
         if sub is not m:
             sub.register_forward_hook(rec)
-    _forward(m, b, k)
-    return top[0]
+    n = len(b)
+    outs = [_forward(m, b[lo:lo + (chunk or n)], k[lo:lo + (chunk or n)]) for lo in range(0, n, chunk or n)]
+    return torch.cat([p for p, _ in outs]), torch.cat([v for _, v in outs]), top[0]
+
+
+def max_activation(module, b, k):
+    """the largest |output| of any submodule in the float64 forward"""
+    return float64_outputs_and_max_activation(module, b, k)[2]
 
 
 def leave_one_out(cfg, seed=None, amp=None, B=LOO_BOARDS):
@@ -323,6 +330,45 @@ def base_net(cfg, module, device='cpu', dtype=torch.float32):
     sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
     kw = dict(num_players=shape(cfg)[0]) if takes_p else {}
     return cls(sd, device=device, dtype=dtype, **kw)
+
+
+MB1D = ('splendor', 'azul', 'minivilles', 'tlp')    # the tags evaluated by the MobileNet-1d kernel (Splendor 2p: by the V80 kernel too)
+
+
+def forms(cfg):
+    """the operand forms of a config's net: 'default' is evaluator_for's, the others name constructor arguments"""
+    tag = cfg.tag
+    if tag == 'splendor2_v80':
+        return ['default', 'v80-bf16x3', 'v80-f32', 'mb1d-h2', 'mb1d-f32']
+    if tag.startswith(MB1D):
+        return ['default', 'mb1d-f32']
+    if tag == 'santorini1_v89':
+        return ['default', 'split', 'f32']
+    if tag == 'santorini11_v78':
+        return ['default', 'split', 'f32', 'h2-policy1']
+    return ['default']
+
+
+@functools.lru_cache(maxsize=None)
+def _game(cfg):
+    return game(cfg)
+
+
+def evaluator(cfg, form, module, max_batch, device='cuda:0'):
+    """the engine-kernel evaluator of `module`'s weights in one of forms(cfg) (needs the built library and a GPU)"""
+    from azg_amd import nnet
+    from azg_amd.nnet_wrapper import evaluator_for
+    if form == 'default':
+        return evaluator_for(module, _game(cfg), max_batch)
+    sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
+    if form.startswith('v80-'):
+        return nnet.SplendorV80Hip(sd, num_players=2, device=device, max_batch=max_batch, split=form == 'v80-bf16x3', h2=False)
+    base = base_net(cfg, module, device=device)
+    if form.startswith('mb1d-'):
+        return nnet.MobileNet1dHip(base, max_batch=max_batch, h2=form == 'mb1d-h2')
+    hip = nnet.SantoriniV89Hip if cfg.tag == 'santorini1_v89' else nnet.SantoriniV78Hip
+    kw = {'split': dict(split=True, h2=False), 'f32': dict(split=False, h2=False), 'h2-policy1': dict(h2=True, policy2=False)}[form]
+    return hip(base, max_batch=max_batch, **kw)
 
 
 if __name__ == '__main__':

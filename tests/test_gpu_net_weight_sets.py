@@ -16,24 +16,10 @@ pytestmark = pytest.mark.gpu
 
 B = 70
 DEV = 'cuda:0'
-MB1D = ('splendor', 'azul', 'minivilles', 'tlp')
+MB1D = nw.MB1D
 
 
-def _forms(cfg):
-    """the operand forms of a config's net: 'default' is evaluator_for's, the others name constructor arguments"""
-    tag = cfg.tag
-    if tag == 'splendor2_v80':
-        return ['default', 'v80-bf16x3', 'v80-f32', 'mb1d-h2', 'mb1d-f32']
-    if tag.startswith(MB1D):
-        return ['default', 'mb1d-f32']
-    if tag == 'santorini1_v89':
-        return ['default', 'split', 'f32']
-    if tag == 'santorini11_v78':
-        return ['default', 'split', 'f32', 'h2-policy1']
-    return ['default']
-
-
-CASES = [(c.tag, f) for c in nw.configs() for f in _forms(c)]
+CASES = [(c.tag, f) for c in nw.configs() for f in nw.forms(c)]
 # the nets without an after-training check elsewhere (V82 / V83 and Botanik have one).  Akropolis (V31) is not trained here: DESIGN.md
 # §5, "Open fault: training AkropolisV31Module on the GPU"
 TRAINED = [c.tag for c in nw.configs() if c.row.version not in (82, 83, 10, 11, 31)]
@@ -65,22 +51,6 @@ def _module_reference(tag, module):
     return p64, v64, (p32 - p64).abs(), (v32 - v64).abs()
 
 
-def _evaluator(cfg, form, module):
-    from azg_amd import nnet
-    from azg_amd.nnet_wrapper import evaluator_for
-    if form == 'default':
-        return evaluator_for(module, _game(cfg.tag), B)
-    sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
-    if form.startswith('v80-'):
-        return nnet.SplendorV80Hip(sd, num_players=2, device=DEV, max_batch=B, split=form == 'v80-bf16x3', h2=False)
-    base = nw.base_net(cfg, module, device=DEV)
-    if form.startswith('mb1d-'):
-        return nnet.MobileNet1dHip(base, max_batch=B, h2=form == 'mb1d-h2')
-    hip = nnet.SantoriniV89Hip if cfg.tag == 'santorini1_v89' else nnet.SantoriniV78Hip
-    kw = {'split': dict(split=True, h2=False), 'f32': dict(split=False, h2=False), 'h2-policy1': dict(h2=True, policy2=False)}[form]
-    return hip(base, max_batch=B, **kw)
-
-
 def _check(label, ev, tag, p64, v64, dp, dv):
     b, m = _batch(tag)
     pi, v = (t.clone() for t in ev.predict_batch(b, m))
@@ -105,7 +75,7 @@ def test_kernel_matches_float64_module(tag, form, weights):
     from azg_amd import nnet
     cfg = nw.config(tag)
     module, p64, v64, dp, dv = _reference(tag, weights)
-    ev = _evaluator(cfg, form, module)
+    ev = nw.evaluator(cfg, form, module, B, DEV)
     assert isinstance(ev, nnet._EngineNet)
     if form == 'default' and tag.startswith(MB1D):
         assert ev.h2                                                                          # (the f16 x 2 form is the default)
